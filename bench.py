@@ -11,6 +11,12 @@ One step = one forward sweep + one TF-MAD adjoint sweep of the 7-point diffusion
 
 Run: ``python bench.py [--gpus N] [--steps K] [--warmup W] [--workload W] [--edge E]``; N>1 via
 ``torch.distributed.run --nproc-per-node N``.
+
+A plain run does only what the headline figure needs: set-up, W warmup steps, K timed steps, the JSON line (its
+roofline figures come from the timed steps' own events). ``--full`` adds every measurement that takes runs of its own:
+the secondary workload (config 5), the CPU baseline, the default-engine rerun and, with ``--kernel-only``, the raw
+kernel loop. ``--dump-outputs DIR`` writes what the last timed step computed (``out`` and the gradient ``diffu``) as
+``DIR/<name>.npy``, float32, whole or as a fixed seeded sample of ``DUMP_ELEMS`` cells per array.
 """
 import argparse
 import json
@@ -53,8 +59,48 @@ def parse():
                    help='cube edge (default: the workload\'s BASELINE size, 1024 / 768)')
     p.add_argument('--no-cpu-baseline', action='store_true')
     p.add_argument('--cpu-seconds', type=float, default=12.0, help='budget of the CPU baseline sample')
-    p.add_argument('--kernel-only', action='store_true', help='also time the raw kernel loop')
-    return p.parse_args()
+    p.add_argument('--kernel-only', action='store_true', help='also time the raw kernel loop (with --full)')
+    p.add_argument('--full', action='store_true',
+                   help='also run what the headline figure does not need: the secondary workload, the CPU baseline, '
+                        'the default-engine rerun and (--kernel-only) the raw kernel loop; without it --secondary, '
+                        '--cpu-seconds and --kernel-only have no effect')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='after the timed steps write the outputs of the last one (out, diffu of the timed workload) as '
+                        'DIR/<name>.npy, float32; arrays beyond DUMP_ELEMS cells as a fixed seeded sample')
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error('--steps must be at least 1')
+    return args
+
+
+# --dump-outputs: cells kept per array (two arrays of 4 Mi float32 = 32 MiB in all; at N>1 each rank keeps its share
+# of its slab); larger outputs are sampled at flat indices drawn from numpy's default_rng(DUMP_SEED), the same in
+# every run and build
+DUMP_ELEMS = 4 << 20
+DUMP_SEED = 20240531
+
+
+def dump_outputs(directory, arrays, rank, world):
+    """Write ``{name: tensor}`` as ``directory/<name>.npy`` (``<name>_rank<r>.npy`` at N>1, each rank its slab),
+    float32. Returns what was written, for the JSON line."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    keep = DUMP_ELEMS // max(1, world)
+    written = {}
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        sampled = flat.numel() > keep
+        if sampled:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), size=keep))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.to(torch.float32).cpu().numpy()
+        if not sampled:
+            a = a.reshape(tuple(t.shape))
+        fname = f'{name}.npy' if world == 1 else f'{name}_rank{rank}.npy'
+        np.save(os.path.join(directory, fname), a)
+        written[fname] = {'shape': list(a.shape), 'of': list(t.shape), 'sampled': sampled}
+    return written
 
 
 def cpu_model():
@@ -189,10 +235,11 @@ def roofline(name, r, world):
             'bytes_per_launch': r['bytes_fwd'], 'bytes_per_step': 2 * wl['bytes'] * r['cells']}
 
 
-def run_workload(name, edge, args, world, rank, distributed, extras, warmup=None):
+def run_workload(name, edge, args, world, rank, distributed, extras, warmup=None, dump=None):
     """Warmup, then EXACTLY ``args.steps`` timed fwd+bwd steps of workload ``name`` through the drop-in path
     (1 GPU: the op; N GPUs: this rank's z-slab through ``ZSlabOp.autograd_function()``), bracketed by barrier +
-    synchronize, max over ranks. Returns the figures of the JSON line."""
+    synchronize, max over ranks. ``dump``: a directory the last timed step's output and gradient are written to
+    after the clock has stopped. Returns the figures of the JSON line."""
     import torch
     import torch.distributed as dist
 
@@ -245,7 +292,9 @@ def run_workload(name, edge, args, world, rank, distributed, extras, warmup=None
     del probe
     uu = u.requires_grad_(True)
 
-    def step(record):
+    last = {}
+
+    def step(record, keep=False):
         e0 = torch.cuda.Event(enable_timing=True)
         e1 = torch.cuda.Event(enable_timing=True)
         e2 = torch.cuda.Event(enable_timing=True)
@@ -254,6 +303,8 @@ def run_workload(name, edge, args, world, rank, distributed, extras, warmup=None
         e1.record(stream)
         o.backward(d)
         e2.record(stream)
+        if keep:                                   # what a caller of the path receives: the output and the gradient
+            last.update(out=o.detach(), diffu=uu.grad)
         uu.grad = None
         if record:
             ev.append((e0, e1, e2))
@@ -286,8 +337,8 @@ def run_workload(name, edge, args, world, rank, distributed, extras, warmup=None
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step(True)
+    for k in range(args.steps):
+        step(True, keep=dump is not None and k == args.steps - 1)
     torch.cuda.synchronize()
     if distributed:
         dist.barrier()
@@ -297,6 +348,10 @@ def run_workload(name, edge, args, world, rank, distributed, extras, warmup=None
         t = torch.tensor([elapsed], dtype=torch.float64, device='cuda')
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
+    dumped = None
+    if dump is not None:
+        dumped = dump_outputs(dump, last, rank, world)
+        last.clear()
 
     fwd_ms = sum(a.elapsed_time(b) for a, b, _ in ev) / len(ev)
     bwd_ms = sum(b.elapsed_time(c) for _, b, c in ev) / len(ev)
@@ -357,7 +412,7 @@ def run_workload(name, edge, args, world, rank, distributed, extras, warmup=None
     out = dict(n=n, zl=zl, value=value, ms_per_step=ms_per_step, fwd_ms=fwd_ms, bwd_ms=bwd_ms, achieved=achieved,
                ksha=kernel_sha(fwd_k, bwd_k), warmup_steps=i,
                achieved_fwd=achieved_fwd, achieved_bwd=achieved_bwd, bytes_fwd=bytes_fwd, kname=kname,
-               cells=cells_total, extra=result_extra, zop=zop_keep)
+               cells=cells_total, extra=result_extra, zop=zop_keep, dumped=dumped)
     del uu, u, d, fn, op
     torch.cuda.synchronize()
     torch.cuda.empty_cache()
@@ -385,9 +440,10 @@ def main():
         else:
             dist.init_process_group(backend)
 
-    primary = run_workload(args.workload, args.edge, args, world, rank, distributed, extras=True)
+    primary = run_workload(args.workload, args.edge, args, world, rank, distributed, extras=args.full,
+                           dump=args.dump_outputs)
     secondary = None
-    if args.secondary != 'none' and args.secondary != args.workload:
+    if args.full and args.secondary != 'none' and args.secondary != args.workload:
         # BASELINE config 5 measured in the same run (the driver's scaling runs call bench.py with its default
         # workload only): same path, same timing rules, its own barrier + max-over-ranks clock
         secondary = run_workload(args.secondary, args.secondary_edge, args, world, rank, distributed, extras=False,
@@ -399,7 +455,7 @@ def main():
     result_extra = primary['extra']
     zop = primary['zop']
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         # after the timed loop, at every N (north_star: the CPU path "in the same run"); the other ranks
         # wait at the barrier below
         try:
@@ -433,7 +489,12 @@ def main():
             'hbm_roofline_frac_step': round(achieved / HBM_PEAK_GBS, 4),
             'roofline': roofline(args.workload, primary, world),
             'cpu_baseline': cpu,
+            'full': args.full,
         }
+        if primary['dumped'] is not None:
+            res['dump_outputs'] = {'dir': args.dump_outputs, 'files': primary['dumped'], 'dtype': 'float32',
+                                   'sample': f'arrays beyond {DUMP_ELEMS // world} cells: sorted flat indices '
+                                             f'numpy default_rng({DUMP_SEED}).integers(0, cells, {DUMP_ELEMS // world})'}
         if secondary is not None:
             w2 = WORKLOADS[args.secondary]
             n2 = secondary['n']

@@ -14,13 +14,13 @@ for V in "$@"; do
   N="${V:-default}"; N="${N//[=,]/_}"
   export PSAD_MARCH="$V"
   [ -z "$V" ] && unset PSAD_MARCH
-  timeout -k 10 200 python bench.py --workload stencil27_f16 --secondary none --steps 3 --warmup 1 --no-cpu-baseline \
+  timeout -k 10 200 python bench.py --workload stencil27_f16 --secondary none --steps 3 --warmup 1 --full --no-cpu-baseline \
       > "$OUT/bsync_${TAG}_${N}_warm.log" 2>&1 || { echo "warm $N failed"; exit 1; }
   i=0
   for P in "$P1" "$P2"; do
     i=$((i+1))
     (cd /tmp && timeout -s KILL 200 rocprofv3 --pmc $P --output-format csv -d "$OUT/bsync_${TAG}_${N}_$i" -o pmc -- \
-        python "$ROOT/bench.py" --workload stencil27_f16 --secondary none --steps 3 --warmup 1 --no-cpu-baseline \
+        python "$ROOT/bench.py" --workload stencil27_f16 --secondary none --steps 3 --warmup 1 --full --no-cpu-baseline \
         > "$OUT/bsync_${TAG}_${N}_$i.log" 2>&1) || { echo "pmc $N $i failed"; exit 1; }
   done
   echo "== $N (PSAD_MARCH='$V')" >> "$OUT/bsync_${TAG}.txt"
