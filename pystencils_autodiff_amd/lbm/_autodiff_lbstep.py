@@ -383,8 +383,9 @@ class AutoDiffLatticeBoltzmannStep:
 
     def set_boundary_including_adjoint(self, boundary_condition, slice_obj=None, mask_callback=None, mask_array=None,
                                        adjoint_boundary_condition=None):
-        """Set ``boundary_condition`` (a ``Boundary``: ``NoSlip``, ``UBB``, ``FixedDensity``, or any boundary whose
-        link reads only the fluid cell's own pdfs, ``boundaries.link_form``) on the selected cells for the forward
+        """Set ``boundary_condition`` (a ``Boundary``: ``NoSlip``, ``UBB``, ``FixedDensity``, any boundary whose
+        link reads only the fluid cell's own pdfs, or a ``NeighbourBoundary`` — ``FreeSlip``, ``ZeroGradientOutflow`` —
+        whose link reads neighbouring fluid cells, ``boundaries.link_form``) on the selected cells for the forward
         AND the adjoint steps (the reference's signature; the adjoint condition defaults to
         ``AdjointBoundaryCondition(bc)``, derived from the forward link by AD)."""
         if not isinstance(boundary_condition, Boundary) or \
@@ -428,12 +429,12 @@ class AutoDiffLatticeBoltzmannStep:
         return self._flag_dev
 
     def _fix_mask(self):
-        """The fluid cells next to link-program walls (``FIX_BIT``: the HIP fix-up kernels' list), None if no
-        boundary is a link program."""
+        """The fluid cells next to link-program walls, and the fluid cells that neighbour links of those read
+        (``FIX_BIT``: the HIP fix-up kernels' list), None if no boundary is a link program."""
         progs = self._programs()
         if progs is None:
             return None
-        return fix_cells(self._boundary.flags, self.method, [k for k, p in enumerate(progs) if p is not None])
+        return fix_cells(self._boundary.flags, self.method, [k for k, p in enumerate(progs) if p is not None], progs)
 
     def _cells_arg(self):
         """The fix-up kernels' cell list (int32 on the device), None without link programs (or on the CPU)."""

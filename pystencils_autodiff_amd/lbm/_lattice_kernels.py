@@ -91,7 +91,39 @@ def _emit(stencil, compressible, ctype, walls, target, idx, addr='ptr', links=No
     cell too (so it runs in the same fix-up launch), the main kernel's thread x zeroes the entry and both the
     writer's value and G_k arrive by atomic adds — two addends onto zero, the same sum in either order, so the result
     is the one the former second fix-up launch (``out += G`` after every other store) gave. The lattice's bulk runs
-    the plain adjoint (measured: profiles/r05_lbm_pressure.jsonl, r06_lbm_fix_merge.jsonl)."""
+    the plain adjoint (measured: profiles/r05_lbm_pressure.jsonl, r06_lbm_fix_merge.jsonl).
+
+    NEIGHBOUR LINKS (``boundaries.neighbour_link_program``: a program row of four, ``(lines, value, jac, offsets)``,
+    Jacobian entries ``(k, lines_k, J, o)``): the link of a pulled component j may read ``src_k(x + c_o)``. It is taken
+    where every cell ``x + c_o`` it reads is fluid — bit ī_o of the cell's OWN mask word says so (it is the neighbour's
+    ``SELF_BIT``, already in a register) — and is the bounce-back otherwise: the wall id's table row is (α, β, γ) =
+    (1, 0, 1), so the fused path has made ``f_j = src_ī(x)`` before the link's ``case`` and scatters ``v_j`` to
+    ``(x, ī_j)`` after it. A taken link replaces both: the forward overwrites ``f_j``; the adjoint adds ``J·v_j`` into
+    ``out_k(x + c_o)`` and drops the scatter to ``(x, ī_j)`` (C: the first pass, which writes every entry once, stores
+    a zero there; HIP: the store is skipped). The C target does the adds in the second pass (``rho_adj`` holds ``v_j``),
+    which now writes OTHER cells from other OpenMP threads: with neighbour links every update of that pass is an
+    ``omp atomic`` one. HIP: the adds are ``atomicAdd`` in the fix-up launch, under the rule above, re-derived for
+    targets in other cells:
+      * listed cells (``fix_cells``, ``FIX_BIT``) are the fluid cells next to a program wall AND every fluid cell a
+        neighbour link of those can read; ``gq_all`` holds every component k a Jacobian entry names (at the cell or at
+        an offset) and every direction d with a neighbour link. So every atomic add of the fix-up launch — G_k, J·v,
+        and the regular scatter's adds below — lands on an entry (listed cell, component in ``gq_all``): call these
+        the E entries.
+      * the main launch never adds atomically. Its thread of a listed cell y only zeroes: E entry (y, q) is zeroed
+        iff its regular writer runs in the fix-up launch (y + c_q a wall: y itself, bounced; or y + c_q listed);
+        otherwise the writer is an unlisted fluid cell, which stores the entry in the main launch and nobody zeroes
+        it. One plain write per E entry in the main launch, then.
+      * in the fix-up launch every scatter store whose target is an E entry is an atomic add (bounced: the cell
+        itself is listed, atomic iff ī_j in ``gq_all``; to x − c_j: atomic iff j in ``gq_all`` and that cell has
+        ``FIX_BIT``); its remaining plain stores go to entries that are not E, which receive no add at all.
+      Hence no entry is written by a plain store in the launch that atomically adds into it; the stores of the main
+      launch come first in stream order; and an E entry whose regular writer is in the fix-up launch starts from zero
+      and receives that writer's value as one of the adds. A taken neighbour link's entry (x, d) has no regular
+      writer left: it is d in ``gq_all`` that gets it zeroed (x + c_d is a wall), and other links may add into it.
+      Bitwise reproducibility: own-cell programs and flat neighbour-link walls put at most two nonzero addends on an
+      entry (one order-independent sum); neighbour links can put three or more on one (corners, a cell read by
+      several links) — there, and only there, the result may differ in the last bit from run to run. Lattices
+      without neighbour links get the source they always had, to the byte."""
     D, Q = stencil.D, stencil.Q
     dirs = [tuple(d) for d in stencil.directions]
     w = [float(x) for x in stencil.weights]
@@ -138,8 +170,31 @@ def _emit(stencil, compressible, ctype, walls, target, idx, addr='ptr', links=No
             L.append(f'{qual} {nm}[{len(vals)}] = {{{", ".join(vals)}}};')
     low = f'{(1 << Q) - 1}u'                 # neighbour-mask bits of the Q directions
     # the components q of a listed cell x that receive G_q = Σ_j J_jq v_j (link programs' Jacobian columns)
-    gq_all = sorted({q for pg in (programs or ()) if pg is not None for row in pg if row is not None
-                     for q, _, _ in row[2]}) if gen else []
+    prows = [(d, row) for pg in (programs or ()) if pg is not None for d, row in enumerate(pg) if row is not None] \
+        if gen else []
+    # neighbour links (``boundaries.neighbour_link_program``: rows of four, Jacobian entries with an offset index)
+    nb = any(len(row) > 3 for _, row in prows)
+    # ... plus, for neighbour links, the components they add into at the cells they read and the link's own direction
+    # d (the entry the replaced bounce-back would have written: zeroed, it receives adds only)
+    gq_all = sorted({r[0] for _, row in prows for r in row[2]} | {d for d, row in prows if len(row) > 3})
+    # the components with Jacobian entries at the cell itself (the G accumulators)
+    g_own = sorted({r[0] for _, row in prows for r in row[2] if len(r) < 4 or r[3] == 0})
+
+    def omask(pg):
+        """Mask bits of the cells a neighbour link reads (bit ī_o of a cell's mask: x + c_o is a wall — the same
+        fact as that cell's own ``SELF_BIT``, without loading its mask word)."""
+        return f'{sum(1 << inv[o] for o in pg[3])}u'
+
+    def okey(o):
+        return key(dirs[inv[o]])                    # x + c_o = x − c_ī(o)
+
+    def nb_loads(code, rd):
+        """Loads of the neighbours' pdfs a program's code reads (``const T n<o>_<k> = src_k(x + c_o);``)."""
+        used = sorted({(int(o), int(k)) for o, k in re.findall(r'\bn(\d+)_(\d+)\b', code)})
+        return ' '.join(f'const {ct} n{o}_{k} = {rd(k, okey(o))};' for o, k in used)
+
+    def out_ptr(k, kk):
+        return f'(T*)((char*)out + oo_{kk} + (unsigned)({k} * o_qb))' if buf else f'out + (IDX){k} * o_q + oo_{kk}'
 
     def c_(v):
         return f'({ct}){_c(v)}'
@@ -298,9 +353,15 @@ def _emit(stencil, compressible, ctype, walls, target, idx, addr='ptr', links=No
                     if cases:
                         L.append(f'  if ((msk >> {i}) & 1u) switch (id{i}) {{')
                         for wid, pg in cases:
-                            lines, val, _ = pg
+                            lines, val = pg[0], pg[1]
                             body = ' '.join(lines) + f' f{i} = {val};'
                             ld = '' if hoisted else own_loads(body, lambda q: load(prefix, arr, q, f'{prefix}o_{centre}'))
+                            if len(pg) > 3:
+                                # a neighbour link: taken where every cell it reads is fluid, else f_i stays the
+                                # bounce-back the table row (1, 0) made
+                                nl = nb_loads(body, lambda q, kk: load(prefix, arr, q, f'{prefix}o_{kk}'))
+                                L.append(f'    case {wid}: if (!(msk & {omask(pg)})) {{ {ld} {nl} {body} }} break;')
+                                continue
                             L.append(f'    case {wid}: {{ {ld} {body} }} break;')
                         L.append('    default: break;\n  }')
             else:
@@ -475,7 +536,7 @@ def _emit(stencil, compressible, ctype, walls, target, idx, addr='ptr', links=No
         # of the kernel's latency-bound chain waits on the mask or on an id
         used = sorted({int(m) for pg in programs if pg is not None for row in pg if row is not None
                        for m in re.findall(r'\bc(\d+)\b', ' '.join(row[0]) + ' ' + row[1] + ' ' +
-                                           ' '.join(' '.join(jl) + ' ' + je for _, jl, je in row[2]))})
+                                           ' '.join(' '.join(r[1]) + ' ' + r[2] for r in row[2]))})
         if used:
             L.append('  ' + ' '.join(f'const {ct} c{q} = {load("s", "src", q, f"so_{centre}")};' for q in used))
         if links is not None and walls:
@@ -485,8 +546,9 @@ def _emit(stencil, compressible, ctype, walls, target, idx, addr='ptr', links=No
     moments(L)
     if rho_links:
         L.append(f'  {ct} Rr = 0;')             # Σ_j βρ_j v_j over the cell's density-weighted links
-    if gq:
-        L.append(f'  {ct} ' + ', '.join(f'G{q} = 0' for q in gq) + ';')      # Σ_j J_jq v_j (link programs)
+    gown = g_own if fix else []
+    if gown:
+        L.append(f'  {ct} ' + ', '.join(f'G{q} = 0' for q in gown) + ';')      # Σ_j J_jq v_j (link programs)
     if mrt is not None:
         # h = Aᵀ g
         for i in range(Q):
@@ -584,14 +646,28 @@ def _emit(stencil, compressible, ctype, walls, target, idx, addr='ptr', links=No
         else:
             L.append(f'  {{ {vq}{ct} v = (({ct})1 - omega) * g{j} + omega * (A + {du});')
         k = key(dirs[j])
+        taken = ''                          # (fix-up kernel) guard of the scatter store: not where a neighbour link is taken
         if walls and any(dirs[j]) and links is not None:
             if rho_links:
                 L.append(f'    if ((msk >> {j}) & 1u) Rr += lk_gr[id{j} * {Q} + {j}] * v;')
             cases = program_cases(j) if adj_progs else []
             if cases and fix:
                 # a program-linked component: Σ_j J_jq(c) v_j (c: the cell's own pre-streaming pdfs)
+                if any(len(pg) > 3 for _, pg in cases):
+                    L.append('    int tk = 0;')
+                    taken = 'if (!tk) { '
                 L.append(f'    if ((msk >> {j}) & 1u) switch (id{j}) {{')
                 for wid, pg in cases:
+                    if len(pg) > 3:
+                        # a neighbour link, where every cell it reads is fluid: J·v into the cells it read (atomic
+                        # adds: those entries are zeroed or stored by the main launch), and no bounce-back store
+                        # (``tk``: the zeroed entry of direction ī_j stays as it is)
+                        rows = ' '.join('{ ' + ' '.join(r[1]) +
+                                        (f' atomicAdd({out_ptr(r[0], okey(r[3]))}, (T)(({r[2]}) * v)); }}' if r[3] else
+                                         f' G{r[0]} += ({r[2]}) * v; }}') for r in pg[2])
+                        nl = nb_loads(rows, lambda q, kk: load('s', 'src', q, f'so_{kk}'))
+                        L.append(f'      case {wid}: if (!(msk & {omask(pg)})) {{ {nl} {rows} tk = 1; }} break;')
+                        continue
                     if len({jl for _, jl, _ in pg[2]}) == 1:
                         # one set of temporaries for the whole row (FixedDensity.program): emitted once
                         rows = ' '.join(pg[2][0][1]) + ' ' + ' '.join(f'G{q} += ({je}) * v;' for q, _, je in pg[2])
@@ -602,8 +678,15 @@ def _emit(stencil, compressible, ctype, walls, target, idx, addr='ptr', links=No
             elif cases:
                 # a program-linked component: its v for the second pass (the Jacobian row is evaluated there)
                 L.append(f'    if ((msk >> {j}) & 1u) switch (id{j}) {{')
-                L.append('      ' + ' '.join(f'case {wid}:' for wid, _ in cases) +
-                         f' rho_adj[(IDX){j} * {ncells} + {cell}] = v; break;')
+                own = [wid for wid, pg in cases if len(pg) < 4]
+                if own:
+                    L.append('      ' + ' '.join(f'case {wid}:' for wid in own) +
+                             f' rho_adj[(IDX){j} * {ncells} + {cell}] = v; break;')
+                for wid, pg in cases:
+                    if len(pg) > 3:
+                        # a neighbour link where it is taken: v for the second pass, a zero for the bounce-back's entry
+                        L.append(f'      case {wid}: if (!(msk & {omask(pg)})) {{ rho_adj[(IDX){j} * {ncells} + {cell}] '
+                                 '= v; v = 0; } break;')
                 L.append('      default: break;\n    }')
             L.append(f'    if ((msk >> {j}) & 1u) v *= lk_g[id{j} * {Q} + {j}];')
         if walls and any(dirs[j]) and fix and (j in gq or inv[j] in gq):
@@ -614,12 +697,13 @@ def _emit(stencil, compressible, ctype, walls, target, idx, addr='ptr', links=No
             if buf:
                 L.append(f'    const unsigned vs = ((msk >> {j}) & 1u) ? oo_{centre} + (unsigned)({inv[j]} * o_qb) : '
                          f'oo_{k} + (unsigned)({j} * o_qb);')
-                L.append(f'    if (((msk >> {j}) & 1u) ? {ab} : {an}) atomicAdd((T*)((char*)out + vs), (T)v); '
-                         f'else {store_v("o", "vs", "v")} }}')
+                L.append(f'    {taken}if (((msk >> {j}) & 1u) ? {ab} : {an}) atomicAdd((T*)((char*)out + vs), (T)v); '
+                         f'else {store_v("o", "vs", "v")} }}' + (' }' if taken else ''))
             else:
                 L.append(f'    const IDX vs = ((msk >> {j}) & 1u) ? (IDX){inv[j]} * o_q + oo_{centre} : (IDX){j} * o_q + '
                          f'oo_{k};')
-                L.append(f'    if (((msk >> {j}) & 1u) ? {ab} : {an}) atomicAdd(out + vs, (T)v); else out[vs] = (T)v; }}')
+                L.append(f'    {taken}if (((msk >> {j}) & 1u) ? {ab} : {an}) atomicAdd(out + vs, (T)v); '
+                         'else out[vs] = (T)v; }' + (' }' if taken else ''))
         elif walls and any(dirs[j]):
             if buf:
                 L.append(f'    const unsigned vs = ((msk >> {j}) & 1u) ? oo_{centre} + (unsigned)({inv[j]} * o_qb) : '
@@ -638,11 +722,11 @@ def _emit(stencil, compressible, ctype, walls, target, idx, addr='ptr', links=No
     if rho_links:
         # the density term: slot Q of the scratch array with inline link programs, its only slot without
         L.append(f'  if (msk & {low}) rho_adj[' + (f'(IDX){Q} * {ncells} + ' if inl else '') + f'{cell}] = Rr;')
-    if gq:
+    if gown:
         # out_q(x) += G_q: after the main launch's store of that entry, or (zeroed entry) in either order with this
         # launch's own atomic store into it — two addends onto zero, so the sum is the same either way
         L.append('  ' + ' '.join(f'atomicAdd(' + (f'(T*)((char*)out + oo_{centre} + (unsigned)({q} * o_qb))' if buf else
-                                                 f'out + (IDX){q} * o_q + oo_{centre}') + f', G{q});' for q in gq))
+                                                 f'out + (IDX){q} * o_q + oo_{centre}') + f', G{q});' for q in gown))
     L.append('}')
     if two:
         # second adjoint pass: the density term of the cell's links reaches every component of the cell, whose
@@ -652,14 +736,20 @@ def _emit(stencil, compressible, ctype, walls, target, idx, addr='ptr', links=No
         L.append(f'  const unsigned msk = nbmask[{cell}];')
         L.append(f'  if (((msk >> {SELF_BIT}) & 1u) || !(msk & {low})) return;')
         L.append('  const IDX oc = ' + ' + '.join(f'(IDX){a} * o_{a}' for a in axes) + ';')
+        # with neighbour links (C target) this pass adds into OTHER cells too, from other OpenMP threads: every update of
+        # the pass is then an atomic one
+        at = '_Pragma("omp atomic") ' if nb and not hip else ''
         if rho_links:
             L.append(f'  const {ct} R = rho_adj[' + (f'(IDX){Q} * {ncells} + ' if inl else '') + f'{cell}];')
             for q in range(Q):
-                L.append(f'  out[(IDX){q} * o_q + oc] += R;')
+                L.append(f'  {at}out[(IDX){q} * o_q + oc] += R;')
         if inl:
             # Σ_j J_jk(c) v_j over the cell's program-linked components (c: the cell's own pre-streaming pdfs)
             wrap_lines(L)
             L.append('  const IDX sc = ' + ' + '.join(f'(IDX){a} * s_{a}' for a in axes) + ';')
+            if nb:
+                neighbour_offsets(L, 's')
+                neighbour_offsets(L, 'o')
             for j in range(Q):
                 cases = program_cases(j)
                 if not cases:
@@ -668,7 +758,15 @@ def _emit(stencil, compressible, ctype, walls, target, idx, addr='ptr', links=No
                 L.append(f'    const {ct} v = rho_adj[(IDX){j} * {ncells} + {cell}];')
                 L.append(f'    switch (wallid[{ncell(key(dirs[j]))}]) {{')
                 for wid, pg in cases:
-                    rows = ' '.join('{ ' + ' '.join(jl) + f' out[(IDX){q} * o_q + oc] += ({je}) * v; }}'
+                    if len(pg) > 3:
+                        # a neighbour link, where it is taken: J·v into out_k(x + c_o)
+                        rows = ' '.join('{ ' + ' '.join(r[1]) + f' {at}out[(IDX){r[0]} * o_q + ' +
+                                        (f'oo_{okey(r[3])}' if r[3] else 'oc') + f'] += ({r[2]}) * v; }}' for r in pg[2])
+                        ld = own_loads(rows, lambda q: f'({ct})src[(IDX){q} * s_q + sc]')
+                        nl = nb_loads(rows, lambda q, kk: f'({ct})src[(IDX){q} * s_q + so_{kk}]')
+                        L.append(f'      case {wid}: if (!(msk & {omask(pg)})) {{ {ld} {nl} {rows} }} break;')
+                        continue
+                    rows = ' '.join('{ ' + ' '.join(jl) + f' {at}out[(IDX){q} * o_q + oc] += ({je}) * v; }}'
                                     for q, jl, je in pg[2])
                     ld = own_loads(rows, lambda q: f'({ct})src[(IDX){q} * s_q + sc]')
                     L.append(f'      case {wid}: {{ {ld} {rows} }} break;')
@@ -755,16 +853,28 @@ def _emit(stencil, compressible, ctype, walls, target, idx, addr='ptr', links=No
     return '\n'.join(L) + '\n'
 
 
-def fix_cells(flags, stencil, program_ids):
+def fix_cells(flags, stencil, program_ids, programs=None):
     """Bool over the domain: fluid cells with a neighbour ``x − c_i`` (periodic) among the walls of ``program_ids``
-    (the flag ids whose boundary is a link program) — the cells the HIP fix-up kernels recompute."""
+    (the flag ids whose boundary is a link program) — the cells the HIP fix-up kernels recompute. ``programs`` (per
+    flag id None or its link program): also every fluid cell ``x + c_o`` that a neighbour link of such a cell ``x``
+    reads, and so adds its adjoint into (whether or not the link is taken there: a superset costs a thread)."""
     f = np.asarray(flags)
+    axes = tuple(range(f.ndim))
     prog = np.isin(f, np.asarray(sorted(program_ids), dtype=f.dtype))
     near = np.zeros(f.shape, bool)
     for c in stencil.directions:
         if any(c):
-            near |= np.roll(prog, tuple(int(v) for v in c), axis=tuple(range(len(c))))
-    return near & (f == 0)
+            near |= np.roll(prog, tuple(int(v) for v in c), axis=axes)
+    fluid = f == 0
+    for wid, pg in enumerate(programs or ()):
+        for d, row in enumerate(pg or ()):
+            if row is None or len(row) < 4 or not row[3]:
+                continue
+            # the fluid cells x whose link of direction d ends in a wall cell of this id: x + c_d
+            src = fluid & np.roll(f == wid, tuple(-int(v) for v in stencil.directions[d]), axis=axes)
+            for o in row[3]:
+                near |= np.roll(src, tuple(int(v) for v in stencil.directions[o]), axis=axes)
+    return near & fluid
 
 
 def neighbour_mask(flags, stencil, xp, fix=None):

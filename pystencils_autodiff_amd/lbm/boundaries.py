@@ -36,13 +36,23 @@ quadratic in the cell's velocity), a link that weights another population of the
 kind — are LINK PROGRAMS (``link_program``): the forward value and its Jacobian row ``∂f_in/∂pdf(k)`` (read off
 the adjoint object's assignments) printed as C per (wall id, direction) and compiled into the same lattice kernels:
 the forward evaluates the link from the cell's own pre-streaming pdfs, the adjoint accumulates ``Σ_j J_jk v_j`` per
-component k of the cell and adds it in the second pass. A link that reads another cell or another field raises.
+component k of the cell and adds it in the second pass. A plain ``Boundary`` whose link reads another cell, or any
+link that reads another field, raises.
+
+Links that read populations of NEIGHBOURING fluid cells — a specular (free-slip) wall, a zero-gradient outflow —
+are ``NeighbourBoundary`` objects (``FreeSlip``, ``ZeroGradientOutflow``, user subclasses): the right-hand side may
+hold ``pdf[o](k)`` with ``o`` a direction of the stencil, relative to the fluid cell. Their programs
+(``neighbour_link_program``) carry the offsets each link reads and a Jacobian row per (offset, component): the
+forward loads ``src_k(x + o)``, the adjoint adds ``J·v`` into ``out_k(x + o)``. Where a cell ``x + o`` a link reads
+is not a fluid cell (on the periodic lattice), the link is the half-way bounce-back ``pdf(d)`` and its adjoint the
+bounce-back's: the kernels decide that per cell from the neighbour mask.
 """
 import numpy as np
 import sympy as sp
 
-__all__ = ['Boundary', 'NoSlip', 'UBB', 'FixedDensity', 'AdjointNoSlip', 'AdjointBoundaryCondition',
-           'BoundaryHandling', 'LBMethodView', 'make_slice', 'link_coefficients', 'link_program', 'link_form']
+__all__ = ['Boundary', 'NoSlip', 'UBB', 'FixedDensity', 'NeighbourBoundary', 'FreeSlip', 'ZeroGradientOutflow',
+           'AdjointNoSlip', 'AdjointBoundaryCondition', 'BoundaryHandling', 'LBMethodView', 'make_slice',
+           'link_coefficients', 'link_program', 'neighbour_link_program', 'link_form']
 
 
 class _MakeSlice:
@@ -235,6 +245,96 @@ class FixedDensity(Boundary):
 
     def __repr__(self):
         return f'FixedDensity({self.density!r}, {self.name!r})'
+
+
+class NeighbourBoundary(Boundary):
+    """A boundary whose link may read populations of other cells: the right-hand side of ``pdf[c_d](ī_d) ← R_d`` may
+    hold ``pdf[o](k)`` with ``o`` relative to the fluid cell ``x`` and a direction of the method's own stencil
+    (0 included; anything else raises ``NotImplementedError`` naming the offset).
+
+    Contract: ``R_d`` is evaluated on the pre-streaming state. If ANY cell ``x + o``, ``o ≠ 0``, that it reads is not a
+    fluid cell (on the periodic lattice, as every neighbour test of the lattice kernels), the link is the plain
+    half-way bounce-back ``pdf(d)`` and its adjoint the bounce-back's. The kernels decide this per cell at run time
+    from the neighbour mask; no per-link table is built."""
+
+
+def _axis_normal(normal_direction, who):
+    n = tuple(int(v) for v in normal_direction)
+    if any(v != w for v, w in zip(n, normal_direction)) or sorted(abs(v) for v in n) != [0] * (len(n) - 1) + [1]:
+        raise ValueError(f'{who}: normal_direction {tuple(normal_direction)!r} is not a signed unit axis vector')
+    return n
+
+
+class FreeSlip(NeighbourBoundary):
+    """Specular reflection at a flat wall: no friction, no flux. ``normal_direction`` ``n``: a signed unit axis vector
+    pointing from the wall into the fluid. For the link direction ``d`` with ``s = c_d·n``: ``s ≥ 0`` — the bounce-back
+    ``pdf(d)``; else, with the tangential part ``t = c_d − s·n`` and ``m`` the direction ``c_m = c_d − 2t``,
+    ``pdf[c_d](ī_d) ← pdf[t](m)`` (pull form: ``f_{ī_d}(x) = src_m(x + t)``; ``t = 0``: the bounce-back). Where ``x + t``
+    is not a fluid cell the link bounces back (``NeighbourBoundary``). Between two such walls a uniform tangential
+    equilibrium flow is a fixed point of the step. Parity with lbmpy's ``FreeSlip`` is unpinned (lbmpy absent)."""
+
+    def __init__(self, normal_direction, name=None):
+        self.normal_direction = _axis_normal(normal_direction, 'FreeSlip')
+        super().__init__(name if name is not None else 'FreeSlip' + str(self.normal_direction))
+
+    def __call__(self, pdf_field, direction, lb_method, **kwargs):
+        st = _directions(lb_method)
+        c = tuple(int(v) for v in st.directions[direction])
+        n = self.normal_direction
+        if len(n) != len(c):
+            raise ValueError(f'FreeSlip normal {n} has not one component per axis of {st.name}')
+        from .. import ps
+        link = pdf_field[c](st.inverse_direction_index(direction))
+        s = sum(ci * ni for ci, ni in zip(c, n))
+        t = tuple(ci - s * ni for ci, ni in zip(c, n))
+        if s >= 0 or not any(t):
+            return [ps.Assignment(link, pdf_field(direction))]
+        cm = tuple(ci - 2 * ti for ci, ti in zip(c, t))
+        dirs = [tuple(int(v) for v in d) for d in st.directions]
+        return [ps.Assignment(link, pdf_field[t](dirs.index(cm)))]
+
+    def __hash__(self):
+        return hash(('FreeSlip', self.name, self.normal_direction))
+
+    def __eq__(self, other):
+        return isinstance(other, FreeSlip) and self.name == other.name and \
+            self.normal_direction == other.normal_direction
+
+    def __repr__(self):
+        return f'FreeSlip({self.normal_direction!r}, {self.name!r})'
+
+
+class ZeroGradientOutflow(NeighbourBoundary):
+    """An open outlet by copying: for ``c_d·n < 0`` (``n``: signed unit axis vector from the wall into the fluid)
+    ``pdf[c_d](ī_d) ← pdf[n](ī_d)`` — the incoming population is the one of the cell one step inward,
+    ``f_j(x) = src_j(x + n)``; otherwise (and where ``x + n`` is not a fluid cell) the bounce-back. Parity with lbmpy
+    is unpinned (lbmpy absent); this is NOT lbmpy's ``ExtrapolationOutflow``, which carries per-link state."""
+
+    def __init__(self, normal_direction, name=None):
+        self.normal_direction = _axis_normal(normal_direction, 'ZeroGradientOutflow')
+        super().__init__(name if name is not None else 'ZeroGradientOutflow' + str(self.normal_direction))
+
+    def __call__(self, pdf_field, direction, lb_method, **kwargs):
+        st = _directions(lb_method)
+        c = tuple(int(v) for v in st.directions[direction])
+        n = self.normal_direction
+        if len(n) != len(c):
+            raise ValueError(f'ZeroGradientOutflow normal {n} has not one component per axis of {st.name}')
+        from .. import ps
+        inv = st.inverse_direction_index(direction)
+        if sum(ci * ni for ci, ni in zip(c, n)) >= 0:
+            return [ps.Assignment(pdf_field[c](inv), pdf_field(direction))]
+        return [ps.Assignment(pdf_field[c](inv), pdf_field[n](inv))]
+
+    def __hash__(self):
+        return hash(('ZeroGradientOutflow', self.name, self.normal_direction))
+
+    def __eq__(self, other):
+        return isinstance(other, ZeroGradientOutflow) and self.name == other.name and \
+            self.normal_direction == other.normal_direction
+
+    def __repr__(self):
+        return f'ZeroGradientOutflow({self.normal_direction!r}, {self.name!r})'
 
 
 class LBMethodView:
@@ -462,7 +562,8 @@ def link_program(forward_bc, adjoint_bc, lb_method):
         bad = [a for a in rhs.atoms(ps.Field.Access) if a not in own]
         if bad or (rhs.free_symbols - set(rhs.atoms(ps.Field.Access))):
             raise NotImplementedError(f'{forward_bc!r}: the lattice kernels take links of the fluid cell\'s own pdfs '
-                                      f'and constants, got {rhs}')
+                                      f'and constants, got {rhs} (a link that reads neighbouring cells is a '
+                                      'NeighbourBoundary)')
         value = rhs.xreplace(own)
         lines, (val,) = _program_code([value])
         if derived:
@@ -509,13 +610,100 @@ def link_program(forward_bc, adjoint_bc, lb_method):
     return tuple(out)
 
 
+def neighbour_link_program(forward_bc, adjoint_bc, lb_method):
+    """The link programs of a ``NeighbourBoundary``. Per direction ``d``: ``None`` (the rest population, or a link
+    that is the bounce-back ``pdf(d)`` itself: the fused table row (1, 0, 1) carries it) or the extended row form
+    ``(lines, value, jac, offsets)``: ``value`` an expression in the cell's own pdfs ``c<k>`` and the neighbours'
+    ``n<o>_<k>`` = ``pdf[c_o](k)`` (``o``: the stencil's index of the offset); ``jac``: ``((k, lines_k, J, o), …)`` —
+    the adjoint link ``diffpdf[c_o](k) ← J · diffpdf[c_d](ī_d)`` (o = 0: the cell itself); ``offsets``: the sorted
+    nonzero ``o`` the link reads (the cells whose being fluid the kernels test, else the bounce-back applies).
+    The Jacobian is the derivative of the forward link (a derived ``AdjointBoundaryCondition``) or read off the
+    adjoint object's assignments. An offset that is no direction of the stencil raises ``NotImplementedError``."""
+    from .. import ps
+    from .._adjoint_field import AdjointField
+    st = _directions(lb_method)
+    f = ps.fields(f'__pdf({st.Q}): [{st.D}D]')
+    g = AdjointField(f)
+    dirs = [tuple(int(v) for v in c) for c in st.directions]
+    zero = dirs.index((0,) * st.D)
+
+    def where(acc, fld, what):
+        """(offset's direction index, component) of a pdf access."""
+        o = tuple(int(v) for v in acc.offsets)
+        if acc.field != fld:
+            raise NotImplementedError(f'{what}: reads the field {acc.field.name} (links read the pdfs only)')
+        if o not in dirs:
+            raise NotImplementedError(f'{what}: offset {o} is not a direction of {getattr(st, "name", "the stencil")} '
+                                      '(a link reads the fluid cell or its stencil neighbours)')
+        return dirs.index(o), int(acc.index[0])
+
+    def sym(oi, k):
+        return sp.Symbol(f'c{k}' if oi == zero else f'n{oi}_{k}')
+    derived = isinstance(adjoint_bc, AdjointBoundaryCondition) and adjoint_bc.forward_condition == forward_bc and \
+        type(adjoint_bc) is AdjointBoundaryCondition
+    out = []
+    for d in range(st.Q):
+        c = dirs[d]
+        if not any(c):
+            out.append(None)
+            continue
+        inv = st.inverse_direction_index(d)
+        fwd = list(forward_bc(f, d, lb_method))
+        if any(hasattr(a.lhs, 'field') and a.lhs != f[c](inv) for a in fwd):
+            raise NotImplementedError(f'{forward_bc!r}: a link writes one population of the wall cell, got {fwd}')
+        rhs = _inline(fwd, f[c](inv))
+        if rhs is None:
+            raise NotImplementedError(f'{forward_bc!r}: no link assignment to pdf[c_d](inv_d) in {fwd}')
+        rhs = sp.sympify(rhs)
+        reads = {a: where(a, f, f'{forward_bc!r}') for a in rhs.atoms(ps.Field.Access)}
+        if rhs.free_symbols - set(reads):
+            raise NotImplementedError(f'{forward_bc!r}: the lattice kernels take links of pdfs and constants, got {rhs}')
+        if rhs == f(d):
+            out.append(None)                        # the bounce-back: the fused table row
+            continue
+        names = {a: sym(*ok) for a, ok in reads.items()}
+        value = rhs.xreplace(names)
+        lines, (val,) = _program_code([value])
+        jac = []
+        if derived:
+            for a, (oi, k) in sorted(reads.items(), key=lambda it: it[1]):
+                jk = sp.diff(value, names[a])
+                if jk != 0:
+                    jac.append((k, jk, oi))
+        else:
+            bwd = adjoint_bc(g, d, lb_method)
+            allb = list(getattr(bwd, 'all_assignments', bwd))
+            gv = sp.Symbol('__gv')
+            for a in allb:
+                if not hasattr(a.lhs, 'field'):
+                    continue
+                oi, k = where(a.lhs, g, f'{adjoint_bc!r}')
+                r = sp.expand(sp.sympify(_inline(allb, a.lhs)).xreplace({g[c](inv): gv}))
+                jk = sp.diff(r, gv)
+                if sp.expand(r - jk * gv) != 0:
+                    raise NotImplementedError(f'{adjoint_bc!r}: adjoint link of pdf[{dirs[oi]}]({k}) is not linear in '
+                                              f'diffpdf[c_d](inv_d): {r}')
+                jk = sp.expand(jk.xreplace({b: sym(*where(b, f, f'{adjoint_bc!r}'))
+                                            for b in jk.atoms(ps.Field.Access)}))
+                if jk != 0:
+                    jac.append((k, jk, oi))
+        rows = []
+        for k, jk, oi in jac:
+            jl, (je,) = _program_code([jk])
+            rows.append((k, jl, je, 0 if oi == zero else oi))
+        offs = {oi for oi, _ in reads.values()} | {oi for _, _, _, oi in rows}
+        out.append((lines, val, tuple(rows), tuple(sorted(o for o in offs if o and o != zero))))
+    return tuple(out)
+
+
 _FORMS = {}
 
 
 def link_form(forward_bc, adjoint_bc, lb_method):
     """``('affine', link_coefficients(...))`` — the fused (α, β, γ, βρ, γρ) form — or ``('program',
-    link_program(...))``; raises ``NotImplementedError`` for a link neither takes. Memoised per (boundary pair,
-    stencil, compressibility): a D3Q19 ``FixedDensity`` program takes seconds of sympy."""
+    link_program(...))``, or, for a ``NeighbourBoundary``, ``('neighbour', neighbour_link_program(...))``; raises
+    ``NotImplementedError`` for a link none takes (a plain ``Boundary`` that reads another cell among them). Memoised
+    per (boundary pair, stencil, compressibility): a D3Q19 ``FixedDensity`` program takes seconds of sympy."""
     st = _directions(lb_method)
     key = (forward_bc, adjoint_bc, type(adjoint_bc), getattr(st, 'name', None), st.Q,
            getattr(lb_method, 'compressible', None))
@@ -525,10 +713,13 @@ def link_form(forward_bc, adjoint_bc, lb_method):
         key, hit = None, None
     if hit is not None:
         return hit
-    try:
-        res = 'affine', link_coefficients(forward_bc, adjoint_bc, lb_method)
-    except NotImplementedError:
-        res = 'program', link_program(forward_bc, adjoint_bc, lb_method)
+    if isinstance(forward_bc, NeighbourBoundary):
+        res = 'neighbour', neighbour_link_program(forward_bc, adjoint_bc, lb_method)
+    else:
+        try:
+            res = 'affine', link_coefficients(forward_bc, adjoint_bc, lb_method)
+        except NotImplementedError:
+            res = 'program', link_program(forward_bc, adjoint_bc, lb_method)
     if key is not None:
         _FORMS[key] = res
     return res
@@ -618,7 +809,9 @@ class BoundaryHandling:
         """``(tables, programs)``. ``tables``: per flag id ≥ 1 the ``link_coefficients`` of its (forward, adjoint)
         boundary pair, or None when every id is a plain bounce-back (α = γ = 1, β = 0: the kernels' fast path, no id
         loads). ``programs``: None, or per flag id the ``link_program`` of a boundary the fused form does not take
-        (None for the others; its table row is all zeros, so the fused path contributes nothing)."""
+        (None for the others; its table row is all zeros, so the fused path contributes nothing) or the
+        ``neighbour_link_program`` of a ``NeighbourBoundary`` (its table row is the bounce-back's (1, 0, 1): what
+        the link falls back to where a cell it reads is not fluid)."""
         objs = self.objects()
         st = _directions(lb_method)
         zero = tuple((0.0, 0.0, 0.0, 0.0, 0.0) for _ in range(st.Q))
@@ -626,6 +819,11 @@ class BoundaryHandling:
         plain = True
         for k in range(1, len(objs)):
             kind, t = link_form(objs[k], self.adjoints[k], lb_method)
+            if kind == 'neighbour':
+                tables.append(tuple((1.0, 0.0, 1.0, 0.0, 0.0) for _ in range(st.Q)))
+                programs.append(t if any(p is not None for p in t) else None)
+                plain &= programs[-1] is None
+                continue
             if kind == 'program':
                 tables.append(zero)
                 programs.append(t)

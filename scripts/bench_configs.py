@@ -257,7 +257,12 @@ def run_lbm(name, stencil, shape, dtype, T=10, reps=5, compressible=False, walls
     rule = lbm.create_lb_update_rule(stencil, compressible=compressible, data_type=dts, force_model=force_model,
                                      force=force, **mk)
     step = lbm.AutoDiffLatticeBoltzmannStep(rule, domain_size=shape, relaxation_rate=1.5, target='gpu')
-    if walls:
+    if walls == 'freeslip':
+        # a slip channel: free-slip (specular) walls on the first and last rows of axis 1 (neighbour links)
+        n = (0, 1) + (0,) * (D - 2)
+        step.set_boundary_including_adjoint(lbm.FreeSlip(n), lbm.make_slice[:, 0])
+        step.set_boundary_including_adjoint(lbm.FreeSlip(tuple(-v for v in n)), lbm.make_slice[:, -1])
+    elif walls:
         # a channel: no-slip walls on the first and last rows of axis 1
         step.set_boundary_including_adjoint(lbm.NoSlip(), lbm.make_slice[:, 0])
         step.set_boundary_including_adjoint(lbm.NoSlip(), lbm.make_slice[:, -1])
@@ -406,12 +411,15 @@ def main():
             ('lbm_d3q19_f32_192^3_channel', 'D3Q19', (192, 192, 192), torch.float32, True),
             ('lbm_d2q9_f32_2048^2_pressure', 'D2Q9', (2048, 2048), torch.float32, 'pressure'),
             ('lbm_d3q19_f32_192^3_pressure', 'D3Q19', (192, 192, 192), torch.float32, 'pressure'),
+            ('lbm_d2q9_f32_2048^2_freeslip', 'D2Q9', (2048, 2048), torch.float32, 'freeslip'),
+            ('lbm_d3q19_f32_192^3_freeslip', 'D3Q19', (192, 192, 192), torch.float32, 'freeslip'),
             ('lbm_d2q9_f32_2048^2_mrt', 'D2Q9', (2048, 2048), torch.float32, False, 'mrt'),
             ('lbm_d3q19_f32_192^3_mrt', 'D3Q19', (192, 192, 192), torch.float32, False, 'mrt')]
     for name, stencil, shape, dt, walls, *method in lbms:
         if only and name not in only:
             continue
-        run_lbm(name, stencil, shape, dt, walls=walls, method=method[0] if method else 'srt')
+        for _ in range(repeat):
+            run_lbm(name, stencil, shape, dt, walls=walls, method=method[0] if method else 'srt')
 
 
 if __name__ == '__main__':
