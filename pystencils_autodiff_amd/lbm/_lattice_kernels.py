@@ -51,11 +51,14 @@ def _emit(stencil, compressible, ctype, walls, target, idx, addr='ptr', links=No
           force_field=False, trt=None, programs=None, mode='inline', mrt=None):
     """Source of the forward (``lbm_fwd``) and adjoint (``lbm_adj``) kernels.
 
-    ``addr='buf'`` (HIP): every pdf array is one buffer resource (its bytes below 2³²); a component's plane
-    offset ``q·s_q`` rides in the instruction's scalar offset and each distinct neighbour cell's byte offset is
-    ONE 32-bit VGPR shared by all components that pull from it — no 64-bit address arithmetic per access.
-    ``'ptr'``: plain pointers (the C target, and arrays of 4 GiB and more). ``walls``: a ``uint32`` neighbour
-    mask per cell (bit i: ``x − c_i`` is an obstacle; bit ``SELF_BIT``: ``x`` is one), one load per cell.
+    ``addr='buf'`` (HIP): every pdf array is one buffer resource (its bytes below 2³¹: the record count and the
+    components' scalar offsets pass through ``int``); a component's plane offset ``q·s_q`` rides in the
+    instruction's scalar offset and each distinct neighbour cell's byte offset is ONE 32-bit VGPR shared by all
+    components that pull from it — no 64-bit address arithmetic per access. ``'ptr'``: plain pointers (the C target,
+    and arrays of 2 GiB and more: ``LatticeKernels._mode`` switches at 2³¹ bytes). ``idx``: the type of every stride
+    and element offset (``long long`` once an array, or the force field, reaches 2³¹ − 1 elements).
+    ``walls``: a ``uint32`` neighbour mask per cell (bit i: ``x − c_i`` is an obstacle; bit ``SELF_BIT``: ``x`` is
+    one), one load per cell.
     ``links``: None (every wall a plain bounce-back), or per wall id (the flag array's values) the boundary's link
     coefficients per direction (``boundaries.link_coefficients``): a bounced component then becomes
     ``α·src_ī(x) + β`` (id of the wall cell ``x − c_i`` from the flag array) and its adjoint is scaled by γ.
@@ -982,7 +985,9 @@ class LatticeKernels:
     def build(self):
         from ..backends import hip_runtime as rt
         if self.target == 'gpu':
-            return [rt.compile_hip(self.source('int', a, f), name='psad_lbm.hip') for a in ('buf', 'ptr')
+            # both addressing modes of small arrays, and what arrays of 2³¹ − 1 elements and more take
+            return [rt.compile_hip(self.source(i, a, f), name='psad_lbm.hip')
+                    for i, a in (('int', 'buf'), ('int', 'ptr'), ('long long', 'ptr'))
                     for f in ((False, True) if self.programs is not None else (False,))]
         return self._cpu_fn('fwd')
 
@@ -1013,6 +1018,9 @@ class LatticeKernels:
         return sum(abs(int(s)) * (int(n) - 1) for s, n in zip(t.stride(), t.shape)) + 1
 
     def _mode(self, tensors):
+        """``(idx, addr)`` of a launch on these pdf tensors, by the largest reach among them: ``'buf'`` below 2³¹
+        bytes (2 GiB) and ``'ptr'`` from there on (or with a negative stride, or ``PSAD_LBM_ADDR=ptr``); ``'int'``
+        up to 2³¹ − 2 elements and ``'long long'`` from 2³¹ − 1."""
         reach = max(self._reach(t) for t in tensors)
         idx = 'int' if reach < 2 ** 31 - 1 else 'long long'
         esz = tensors[0].element_size()
@@ -1021,13 +1029,37 @@ class LatticeKernels:
             addr = 'ptr'
         return idx, addr
 
+    def _launch_mode(self, tensors, force=None, dforce=None):
+        """``(idx, addr)`` of a ``plan()`` launch: ``_mode`` of the pdf tensors; the force (and its adjoint) is
+        read through plain pointers with IDX offsets, so a far-reaching force field widens ``idx`` alone."""
+        idx, addr = self._mode(tensors)
+        if force is not None and max(self._reach(force), self._reach(dforce) if dforce is not None else 0) \
+                >= 2 ** 31 - 1:
+            idx = 'long long'
+        return idx, addr
+
+    def _arg_format(self, idx, ntensors, nptr, nstrides, fix=False):
+        """``(fmt, index of ω)`` of a ``plan()`` launch's argument buffer (``_pack``): ``nptr`` pointers, the
+        extents, ``nstrides`` strides of type ``idx``, the ``ntensors`` pdf arrays' byte reaches, ω; the fix-up
+        kernel's cell list and its length after them."""
+        code = 'i' if idx == 'int' else 'q'
+        fmt = 'Q' * nptr + 'iii' + code * nstrides + 'q' * ntensors + ('d' if self.ct == 'double' else 'f')
+        return fmt + ('Qi' if fix else ''), len(fmt) - 1
+
+    def _rho_format(self, idx):
+        """``(fmt, index of the src slot or None)`` of a ``rho_plan()`` launch's argument buffer."""
+        code = 'i' if idx == 'int' else 'q'
+        fmt = 'QQQ' + 'iii' + code * 4
+        if self.programs is None:
+            return fmt, None
+        return fmt + 'QQ' + code * 4, len(fmt)
+
     def _common(self, tensors, mask, ids=None):
         self._check(tensors, mask, ids)
-        idx, addr = self._mode(tensors)
         fn_args = []
         for t in tensors:
             fn_args += list(lattice_strides(t, self.stencil.D))
-        return idx, addr, fn_args
+        return fn_args
 
     def _force_check(self, shape, force, dforce, which, xp_tensor=True):
         """The per-cell force (and, for the adjoint, its accumulated adjoint): ``[*domain, D]`` of the pdf dtype,
@@ -1063,16 +1095,13 @@ class LatticeKernels:
         if plan is not None:
             return plan
         self._force_check(tuple(tensors[0].shape), force, dforce, which)
-        idx, addr, strides = self._common(tensors, mask, ids)
+        strides = self._common(tensors, mask, ids)
+        idx, addr = self._launch_mode(tensors, force, dforce)
         if force is not None:
-            # the force is read (and its adjoint accumulated) through plain pointers with IDX offsets
-            if max(self._reach(force), self._reach(dforce) if dforce is not None else 0) >= 2 ** 31 - 1:
-                idx = 'long long'
             strides += list(lattice_strides(force, self.stencil.D))
         dev = tensors[0].device.index
         fn = self._gpu_fn(which + ('_fix' if fix is not None else ''), idx, addr, dev)
         Z, Y, X = self._extent(tensors[0])
-        code = 'i' if idx == 'int' else 'q'
         nblocks = self._blocks(X, Y, Z) if fix is None else -(-int(fix[0].numel()) // FIX_BLOCK)
         reach = [self._reach(t) * t.element_size() for t in tensors]
         ptrs = [t.data_ptr() for t in tensors] + [mask.data_ptr() if mask is not None else 0,
@@ -1081,13 +1110,10 @@ class LatticeKernels:
             ptrs += [force.data_ptr()] + ([dforce.data_ptr()] if which == 'adj' else [])
         if which == 'adj' and self.link_pass:
             ptrs += [0]                                  # the second pass's scratch array (patched per launch)
-        fmt = 'Q' * len(ptrs) + 'iii' + code * len(strides) + 'q' * len(tensors) + \
-            ('d' if self.ct == 'double' else 'f')
+        fmt, om_i = self._arg_format(idx, len(tensors), len(ptrs), len(strides), fix is not None)
         vals = [*ptrs, Z, Y, X, *strides, *reach, float(omega)]
-        om_i = len(fmt) - 1
         if fix is not None:
             # the fix-up kernel: the cell list and its length after the main kernel's arguments
-            fmt += 'Qi'
             vals += [fix[0].data_ptr(), int(fix[0].numel())]
         args = _pack(fmt, *vals)
         plan = self._plans[key] = LaunchPlan(fn, nblocks, args, len(ptrs), dev, _offset(fmt, om_i), fmt[om_i])
@@ -1138,21 +1164,19 @@ class LatticeKernels:
         dev = out.device.index
         fn = self._gpu_fn('adj_rho', idx, addr, dev)
         Z, Y, X = self._extent(out)
-        code = 'i' if idx == 'int' else 'q'
+        fmt, extra_i = self._rho_format(idx)
         if self.programs is None:
-            fmt = 'QQQ' + 'iii' + code * 4
             args = _pack(fmt, out.data_ptr(), mask.data_ptr(), rho.data_ptr(), Z, Y, X,
                          *lattice_strides(out, self.stencil.D))
             nptr = 3
         else:
-            fmt = 'QQQ' + 'iii' + code * 4 + 'QQ' + code * 4
             args = _pack(fmt, out.data_ptr(), mask.data_ptr(), rho.data_ptr(), Z, Y, X,
                          *lattice_strides(out, self.stencil.D), src.data_ptr(), ids.data_ptr(),
                          *lattice_strides(src, self.stencil.D))
             nptr = 3
         plan = self._plans[key] = LaunchPlan(fn, self._blocks(X, Y, Z), args, nptr, dev, None, None)
         if self.programs is not None:
-            plan.extra = _offset(fmt, 3 + 3 + 4)          # the src / ids slots, patched per launch
+            plan.extra = _offset(fmt, extra_i)            # the src / ids slots, patched per launch
         return plan
 
     def forward(self, src, dst, omega, mask=None, stream=None, ids=None, force=None, cells=None):
