@@ -68,13 +68,9 @@ def _lattice_sweeps(step, which, launches, force=None, dforce=None):
     ids = step._ids_arg()
     cells = step._cells_arg()
     om = step._omega_of()
-    mptr = (mask.data_ptr() if mask is not None else 0, ids.data_ptr() if ids is not None else 0)
-    if force is not None:
-        mptr += (force.data_ptr(),) + ((dforce.data_ptr(),) if which == 'adj' else ())
     stream = _torch()._C._cuda_getCurrentRawStream(launches[0][0].device.index)
     rho = K.rho_buffer(launches[0][0]) if which == 'adj' and K.link_pass else None
-    if rho is not None:
-        mptr += (rho.data_ptr(),)
+    mptr = K.tail_ptrs(which, mask, ids, force, dforce, rho)      # once: the launches differ in their pdf arrays only
     plans = {}
     for ts in launches:
         sig = tuple(t.stride() for t in ts)

@@ -16,6 +16,7 @@ from pystencils_autodiff_amd import AdjointField, lbm, ps
 
 OMEGA = 1.3
 GOLDEN = os.path.join(os.path.dirname(__file__), 'golden', 'lattice_source_sha.json')
+GOLDEN_ALL = os.path.join(os.path.dirname(__file__), 'golden', 'lattice_source_sha_all.json')
 
 
 def _init(stencil, shape, compressible, seed=0):
@@ -470,6 +471,101 @@ def test_existing_lattice_sources_unchanged():
     with open(GOLDEN) as fh:
         golden = json.load(fh)
     shas = _source_shas()
+    assert sorted(shas) == sorted(golden)
+    assert [k for k in golden if shas[k] != golden[k]] == []
+
+
+def _all_lattices():
+    """name → a kernel builder (target) of every lattice whose sources ``lattice_source_sha_all.json`` pins: the
+    lattices above, the compile-test families of ``test_lbm_addressing``, the neighbour-link lattices, and one
+    lattice per branch of the source printer that none of those reaches."""
+    from pystencils_autodiff_amd.lbm._lattice_kernels import LatticeKernels
+    from tests import test_lbm_addressing as TA
+    out = dict(_existing_lattices())
+
+    def family(make):
+        def build(target):
+            K = make()._lattice_kernels()          # the families build GPU steps: the C twin from the same description
+            return K if target == 'gpu' else LatticeKernels(
+                K.stencil, K.compressible, K.dtype, K.walls, target, K.links, K.force_model, K.force, K.force_field,
+                trt=K.trt, programs=K.programs, mrt=K.mrt)
+        return build
+    for name, make in TA.COMPILE_FAMILIES:
+        out[f'family-{name}'] = family(make)
+
+    def neighbour(name, stencil, shape, method='srt', compressible=True):
+        return lambda target: _lattice(name, stencil, shape, target, 'float64', method,
+                                       compressible)[0]._lattice_kernels()
+    for name in ('slip', 'mixed', 'outflow2', 'box', 'open'):
+        out[f'nb-{name}-D2Q9'] = neighbour(name, 'D2Q9', (8, 6))
+    for name in ('slip', 'box'):
+        out[f'nb-{name}-D3Q19'] = neighbour(name, 'D3Q19', (8, 6, 5))
+    for method in ('trt', 'mrt'):
+        out[f'nb-open-D2Q9-{method}'] = neighbour('open', 'D2Q9', (8, 6), method)
+    out['nb-open-D2Q9-incompressible'] = neighbour('open', 'D2Q9', (8, 6), compressible=False)
+
+    om = sp.Symbol('omega')
+    methods = dict(srt={}, trt=dict(method='trt'), mrt=dict(method='mrt', relaxation_rates=[om, 1.1, 0.9, 1.2]),
+                   trtrate=dict(method='trt', relaxation_rates=[om, 1.1]))
+
+    def branch(method, model=None, field=False, walls=None, check=lambda K: True):
+        def build(target):
+            kw = dict(methods[method], compressible=True)
+            if model is not None:
+                kw.update(force_model=model, force=ps.fields('F(2): float64[2D]') if field else (1e-3, 2e-3))
+            step = lbm.AutoDiffLatticeBoltzmannStep(lbm.create_lb_update_rule('D2Q9', **kw), domain_size=(8, 6),
+                                                    relaxation_rate=1.3, target=target)
+            if walls is not None:
+                step.set_boundary_including_adjoint(lbm.NoSlip(), (slice(None), 0))
+                step.set_boundary_including_adjoint(
+                    lbm.UBB((0.05, 0.0), density_weighted=True) if walls == 'rho+pressure' else lbm.NoSlip(),
+                    (slice(None), -1))
+            if walls == 'rho+pressure':
+                step.set_boundary_including_adjoint(lbm.FixedDensity(1.02, name='inlet'), (0, slice(1, -1)))
+            assert step._lattice is not None
+            K = step._lattice_kernels()
+            assert check(K)
+            return K
+        return build
+    for method in ('trt', 'mrt'):
+        out[f'branch-guo-{method}'] = branch(method, 'guo')                       # gsplit, a constant force
+        out[f'branch-guo-{method}-field'] = branch(method, 'guo', True)           # gsplit, a force field
+        out[f'branch-simple-{method}-field'] = branch(method, 'simple', True)     # gwm
+    for model in ('simple', 'guo'):
+        out[f'branch-{model}-field-walls'] = branch('srt', model, True, 'noslip', lambda K: K.walls and K.force_field)
+    out['branch-trt-rate'] = branch('trtrate', check=lambda K: K.trt == ('rate', 1.1))
+    out['branch-trt-rate-walls'] = branch('trtrate', walls='noslip', check=lambda K: K.trt == ('rate', 1.1))
+    # a density-weighted wall and a link program in one lattice: scratch slot Q on C, the single slot on HIP
+    out['branch-ubb-rho-pressure'] = branch('srt', walls='rho+pressure',
+                                            check=lambda K: K.rho_links and K.programs is not None)
+    return out
+
+
+def _all_source_shas():
+    """sha256 of every emitted source of ``_all_lattices``: the C target, and the HIP main (and, with link programs,
+    fix-up) modules for both index types in both addressing modes. One kernel object per target; nothing is
+    compiled."""
+    def sha(s):
+        return hashlib.sha256(s.encode()).hexdigest()
+    shas = {}
+    for name, build in _all_lattices().items():
+        shas[f'{name}/c'] = sha(build('cpu').source())
+        K = build('gpu')
+        for idx in ('int', 'long long'):
+            for addr in ('buf', 'ptr'):
+                for fix in ((False, True) if K.programs is not None else (False,)):
+                    shas[f'{name}/hip-{idx.replace(" ", "")}-{addr}{"-fix" if fix else ""}'] = \
+                        sha(K.source(idx, addr, fix=fix))
+    return shas
+
+
+def test_all_lattice_sources_unchanged():
+    """The emitted kernel source of every lattice of ``_all_lattices``, every index type and addressing mode, is
+    byte-identical to what the one-function printer gave before it was split into ``_lattice_source``
+    (``tests/golden/lattice_source_sha_all.json``, generated at the commit before the split by ``_all_source_shas``)."""
+    with open(GOLDEN_ALL) as fh:
+        golden = json.load(fh)
+    shas = _all_source_shas()
     assert sorted(shas) == sorted(golden)
     assert [k for k in golden if shas[k] != golden[k]] == []
 
