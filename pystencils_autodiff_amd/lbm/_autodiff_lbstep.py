@@ -58,11 +58,12 @@ class SimulationResultsTensors:
         self.output_velocity_tensor = output_velocity_tensor
 
 
-def _lattice_sweeps(step, which, launches, force=None, dforce=None):
+def _lattice_sweeps(step, which, launches, force=None, dforce=None, omf=None, domf=None):
     """The lattice kernels over ``launches`` (tensor tuples of ``LatticeKernels.forward`` / ``adjoint``) on the
     current stream: one launch plan per distinct (shapes, strides) — the first, middle and last steps — and only
     the pointers packed per launch. ``force`` (a per-cell force field): bound to every launch; ``dforce``: the
-    adjoint launches add their force adjoints into it."""
+    adjoint launches add their force adjoints into it. ``omf`` / ``domf``: the per-cell relaxation rate and its
+    adjoint, likewise."""
     K = step._lattice_kernels()
     mask = step._flag_arg()
     ids = step._ids_arg()
@@ -70,16 +71,19 @@ def _lattice_sweeps(step, which, launches, force=None, dforce=None):
     om = step._omega_of()
     stream = _torch()._C._cuda_getCurrentRawStream(launches[0][0].device.index)
     rho = K.rho_buffer(launches[0][0]) if which == 'adj' and K.link_pass else None
-    mptr = K.tail_ptrs(which, mask, ids, force, dforce, rho)      # once: the launches differ in their pdf arrays only
+    if which != 'adj':
+        dforce = domf = None
+    # once: the launches differ in their pdf arrays only
+    mptr = K.tail_ptrs(which, mask, ids, force, dforce, rho, omf, domf)
     plans = {}
     for ts in launches:
         sig = tuple(t.stride() for t in ts)
         plan = plans.get(sig)
         if plan is None:
-            plan = plans[sig] = K.plan(which, list(ts), mask, om, ids, force, dforce if which == 'adj' else None)
+            plan = plans[sig] = K.plan(which, list(ts), mask, om, ids, force, dforce, omf=omf, domf=domf)
         plan(tuple(t.data_ptr() for t in ts) + mptr, stream, om)
         # link-program walls (HIP): the fix-up kernels over the cells next to them
-        K.fix_launch(which, list(ts), mask, om, ids, force, dforce if which == 'adj' else None, cells, stream)
+        K.fix_launch(which, list(ts), mask, om, ids, force, dforce, cells, stream, omf, domf)
         if rho is not None:
             # the second pass of density-weighted walls (and, on the CPU, link programs) on this launch's output
             K.rho_pass(ts[2], mask, rho, ts[0], ids, stream)
@@ -103,6 +107,17 @@ def _plain_force_field(force, D):
         if tuple(int(o) for o in c.offsets) != (0,) * D or tuple(int(i) for i in c.index) != (a,):
             return None
     return F
+
+
+def _plain_omega_field(rate, D, dtype):
+    """The relaxation-rate FIELD when the rule's ω is exactly ``w(x)``: a scalar field (no index dimension) of the
+    pdf dtype read at the cell itself, else None."""
+    if not isinstance(rate, ps.Field.Access):
+        return None
+    w = rate.field
+    if w.index_dimensions != 0 or w.spatial_dimensions != D or tuple(int(o) for o in rate.offsets) != (0,) * D:
+        return None
+    return w if np.dtype(w.dtype.numpy_dtype) == np.dtype(dtype) else None
 
 
 def _guess_src_dst_field_from_update_rule(update_rule, src_hint, dst_hint):
@@ -136,7 +151,10 @@ class AutoDiffLatticeBoltzmannStep:
     ``update_rule``: a stream-pull-collide ``AssignmentCollection`` (``lbm.create_lb_update_rule``), its pdf
     fields found as in the reference. ``domain_size``: the spatial extent (without ghost layers).
     ``relaxation_rate`` sets the value of the rule's free scalar (``omega``) unless given as
-    ``kernel_params``. ``target``: ``'gpu'`` (HIP kernels on torch tensors) or ``'cpu'`` (the C kernels on
+    ``kernel_params``; a rule whose rate is read from a field (``relaxation_rate=w.center``, a per-cell ω) has no such
+    scalar: the field is an additional input of the step, ``create_timestep_op(T).apply(pdfs, *extras)`` in name order,
+    and the backward returns its adjoint summed over the steps (a trainable scalar rate: pass ``w0.expand(*domain)``).
+    ``target``: ``'gpu'`` (HIP kernels on torch tensors) or ``'cpu'`` (the C kernels on
     numpy arrays)."""
 
     def __init__(self, update_rule, src_pdf_field='', tmp_pdf_field='', time_constant_fields=(), *args,
@@ -166,12 +184,22 @@ class AutoDiffLatticeBoltzmannStep:
         # periodic kernels (wrapped reads, every cell written) and the transposed adjoint — for the rules of
         # ``create_lb_update_rule`` written through the collision's structure (``create_lb_adjoint_rule``)
         backward = None
+        # the op's forward input fields (the fields the rule reads, sorted by name — transposed_backward's order)
+        read = {a.field for asg in update_rule.all_assignments for a in sp.sympify(asg.rhs).atoms(ps.Field.Access)}
+        self._additional_fields = [f for f in sorted(read, key=str) if f not in (src, tmp)]
+        rr = getattr(update_rule, 'relaxation_rate', None)
+        rate_fields = sorted({a.field for a in sp.sympify(rr).atoms(ps.Field.Access)}, key=str) if rr is not None else []
+        for w in rate_fields:
+            if w.index_dimensions:
+                raise ValueError(f"relaxation-rate field '{w.name}' has an index dimension: a per-cell relaxation rate "
+                                 'is a scalar field (one value per cell)')
         # (a force term that depends on the pdfs — Guo's, through u — is not in that structure: the generic
-        # transposed derivation then; the 'simple' term is a constant and changes no derivative)
+        # transposed derivation then; the 'simple' term is a constant and changes no derivative. Nor is a rate read
+        # from a field — any additional input field: the structured rule has the pdf adjoint only)
         from ._method import force_is_field
         if getattr(update_rule, 'stencil', None) is not None and not time_constant_fields and \
                 getattr(update_rule, 'force_model', None) in (None, 'simple') and \
-                not force_is_field(getattr(update_rule, 'force', None)):
+                not force_is_field(getattr(update_rule, 'force', None)) and not self._additional_fields:
             from ._method import create_lb_adjoint_rule
             backward = create_lb_adjoint_rule(update_rule)
         # the rule's AutoDiffOp (its kernels are the schedule for rules the lattice kernels do not take, and its
@@ -182,9 +210,6 @@ class AutoDiffLatticeBoltzmannStep:
                                    diff_mode='transposed', time_constant_fields=list(time_constant_fields) or None,
                                    constant_fields=list(constant_fields), backward_assignments=backward)
         self._diff_prefix = 'diff'
-        # the op's forward input fields (the fields the rule reads, sorted by name — transposed_backward's order)
-        read = {a.field for asg in update_rule.all_assignments for a in sp.sympify(asg.rhs).atoms(ps.Field.Access)}
-        self._additional_fields = [f for f in sorted(read, key=str) if f not in (src, tmp)]
         scalars = sorted({s for a in update_rule.all_assignments for s in a.rhs.free_symbols
                           if isinstance(s, sp.Symbol) and not isinstance(s, ps.Field.Access)}
                          - {a.lhs for a in update_rule.subexpressions}, key=str)
@@ -199,9 +224,17 @@ class AutoDiffLatticeBoltzmannStep:
         self._arrays = {}
         self._records = None
         # the lattice schedule for the rules of create_lb_update_rule (SRT, stream_pull_collide); walls need it
-        rr = getattr(update_rule, 'relaxation_rate', None)
-        self._omega_of = (lambda: float(self.kernel_params[rr.name])) if isinstance(rr, sp.Symbol) else \
-            ((lambda v=rr: float(v)) if rr is not None else None)
+        # a per-cell rate read as w(x) (a scalar field of the pdf dtype at the cell itself): the lattice kernels take
+        # the field as an array and accumulate its adjoint (their scalar ω argument is then unused); any other rate
+        # expression that reads a field (1/(3 ν(x) + 1/2), an offset read, another dtype) runs on the AutoDiffOp kernels
+        self._omega_field = _plain_omega_field(rr, src.spatial_dimensions, src.dtype.numpy_dtype)
+        if self._omega_field is not None:
+            self._omega_of = lambda: 0.0
+        elif rate_fields:
+            self._omega_of = None
+        else:
+            self._omega_of = (lambda: float(self.kernel_params[rr.name])) if isinstance(rr, sp.Symbol) else \
+                ((lambda v=rr: float(v)) if rr is not None else None)
         # (PSAD_LBM_LATTICE=0: the AutoDiffOp kernels instead — tests of that path, A/B probes)
         force = getattr(update_rule, 'force', None)
         # a per-cell force read as F(x)[a] (the field's centre, component a, for every axis): the lattice kernels
@@ -214,8 +247,8 @@ class AutoDiffLatticeBoltzmannStep:
             self._lattice_force = (getattr(update_rule, 'force_model', None),
                                    None if force is None else tuple(float(v) for v in force)) \
                 if force is None or all(sp.sympify(v).is_number for v in force) else None
-        extras_ok = not self._additional_fields or (self._force_field is not None and
-                                                    self._additional_fields == [self._force_field])
+        extras_ok = set(self._additional_fields) == {f for f in (self._omega_field, self._force_field)
+                                                     if f is not None}
         # TRT: the odd rate from the magic number (a function of the ω argument) or a constant
         self._lattice_trt = None
         trt_ok = True
@@ -475,7 +508,8 @@ class AutoDiffLatticeBoltzmannStep:
             k = self._lattice[(walls, links, programs)] = LatticeKernels(
                 self.method, getattr(self._update_rule, 'compressible', False), self.pdf_field.dtype.numpy_dtype,
                 walls, self._target, links, *self._lattice_force, force_field=self._force_field is not None,
-                trt=self._lattice_trt, programs=programs, mrt=self._lattice_mrt)
+                trt=self._lattice_trt, programs=programs, mrt=self._lattice_mrt,
+                omega_field=self._omega_field is not None)
         return k
 
     # -- kernels -----------------------------------------------------------------------------------
@@ -488,7 +522,8 @@ class AutoDiffLatticeBoltzmannStep:
     def _fwd(self, src, dst, extra):
         if self._lattice is not None:
             return self._lattice_kernels().forward(src, dst, self._omega_of(), self._flag_arg(), ids=self._ids_arg(),
-                                                   force=self._force_arg(extra), cells=self._cells_arg())
+                                                   force=self._force_arg(extra), cells=self._cells_arg(),
+                                                   omf=self._omega_arg(extra))
         kf, _ = self._kernels()
         kf(**{self._pdf_arr_name: src, self._tmp_arr_name: dst}, **extra, **self.kernel_params)
 
@@ -502,8 +537,25 @@ class AutoDiffLatticeBoltzmannStep:
             raise ValueError(f"the update rule reads the force field '{self._force_field.name}': pass its array "
                              "(extra={name: array})") from None
 
+    def _omega_arg(self, extra):
+        """The per-cell relaxation-rate array of the lattice kernels (None without an ω field)."""
+        if self._omega_field is None:
+            return None
+        try:
+            return extra[self._omega_field.name]
+        except (KeyError, TypeError):
+            raise ValueError(f"the update rule reads the relaxation-rate field '{self._omega_field.name}': pass its "
+                             "array (extra={name: array})") from None
+
     def _bwd(self, src, diffdst, diffsrc, extra, extra_adj):
         if self._lattice is not None:
+            domf = None
+            if self._omega_field is not None:
+                name = self._adjoint_name(self._omega_field)
+                if name not in (extra_adj or {}):
+                    raise ValueError(f"the relaxation-rate field's adjoint '{name}' needs an array (extra_adj), "
+                                     'accumulated into')
+                domf = extra_adj[name]
             dforce = None
             if self._force_field is not None:
                 name = self._adjoint_name(self._force_field)
@@ -512,7 +564,7 @@ class AutoDiffLatticeBoltzmannStep:
                 dforce = extra_adj[name]
             return self._lattice_kernels().adjoint(src, diffdst, diffsrc, self._omega_of(), self._flag_arg(),
                                                    ids=self._ids_arg(), force=self._force_arg(extra), dforce=dforce,
-                                                   cells=self._cells_arg())
+                                                   cells=self._cells_arg(), omf=self._omega_arg(extra), domf=domf)
         _, kb = self._kernels()
         kb(**{self._pdf_arr_name: src, 'diff' + self._tmp_arr_name: diffdst, 'diff' + self._pdf_arr_name: diffsrc},
            **extra, **extra_adj, **self.kernel_params)
@@ -608,7 +660,7 @@ class AutoDiffLatticeBoltzmannStep:
                 if lattice:
                     states = [x0] + step._internal_states(T - 1) + [step._alloc(zero=False)]
                     _lattice_sweeps(step, 'fwd', [(states[t], states[t + 1]) for t in range(T)],
-                                    step._force_arg(ex))
+                                    step._force_arg(ex), omf=step._omega_arg(ex))
                 else:
                     states = [x0]
                     for t in range(T):
@@ -656,14 +708,15 @@ class AutoDiffLatticeBoltzmannStep:
                         nxt = out if t == 0 else ping[(T - 1 - t) % 2]
                         launches.append((records[t], cur, nxt))
                         cur = nxt
-                    if step._force_field is None:
+                    if not extras:
                         _lattice_sweeps(step, 'adj', launches)
                         return out
-                    # the force adjoint: every step's adjoint launch adds its share into one zeroed array
-                    F = step._force_arg(ex)
-                    dF = torch.zeros_like(F)
-                    _lattice_sweeps(step, 'adj', launches, F, dF)
-                    return out, dF
+                    # the force / ω adjoint: every step's adjoint launch adds its share into one array, zeroed once
+                    F, W = step._force_arg(ex), step._omega_arg(ex)
+                    dex = {f.name: torch.zeros_like(ex[f.name]) for f in extras}
+                    _lattice_sweeps(step, 'adj', launches, F, None if F is None else dex[step._force_field.name],
+                                    W, None if W is None else dex[step._omega_field.name])
+                    return (out, *[dex[f.name] for f in extras])
                 cur = g
                 acc = {n: torch.zeros_like(x) for n, x in ex.items()}
                 for t in reversed(range(T)):
@@ -682,7 +735,8 @@ class AutoDiffLatticeBoltzmannStep:
     def _field_layout(self, f, t):
         """An additional input tensor in field ``f``'s memory layout (fzyx: components-first) on the step's side."""
         if not self._gpu:
-            return t
+            # (a scalar field may arrive as an expanded scalar, stride 0: its adjoint array needs cells of its own)
+            return t if f.index_dimensions else t.contiguous()
         if f.index_dimensions and f.is_soa:
             from ..zslab import ZSlabOp
             return ZSlabOp._layout(f, t)

@@ -114,8 +114,10 @@ class LatticeKernels:
     bounce-back)."""
 
     def __init__(self, stencil, compressible, dtype, walls, target, links=None, force_model=None, force=None,
-                 force_field=False, trt=None, programs=None, mrt=None):
+                 force_field=False, trt=None, programs=None, mrt=None, *, omega_field=False):
         self.stencil = stencil
+        # ω read per cell from a scalar field ``[*domain]``, its adjoint accumulated by the adjoint launches
+        self.omega_field = bool(omega_field)
         # MRT: (P_ω, C) relaxation matrices as float tuples (``_method.mrt_relaxation_matrices``)
         self.mrt = None if mrt is None else tuple(tuple(tuple(float(v) for v in row) for row in M) for M in mrt)
         self.trt = None if trt is None else (str(trt[0]), float(trt[1]))
@@ -133,7 +135,8 @@ class LatticeKernels:
         # what to print (``source`` fills in the index type, the addressing and the adjoint mode)
         self.spec = spec = LatticeSource(
             stencil, self.compressible, self.ct, self.walls, self.links, programs, force_model, self.force,
-            self.force_field, self.trt, self.mrt, target='hip' if target == 'gpu' else 'c')
+            self.force_field, self.trt, self.mrt, target='hip' if target == 'gpu' else 'c',
+            omega_field=self.omega_field)
         # density-weighted links: the adjoint takes a second pass (lbm_adj_rho) over a per-cell scratch array
         self.rho_links = spec.rho_links
         # link programs (boundaries.link_program). C: inline, a Q-component scratch array per cell and the second
@@ -199,13 +202,15 @@ class LatticeKernels:
         if min(shape[:-1]) < 2:
             raise ValueError('the periodic lattice needs at least 2 cells per axis')
 
-    def tail_ptrs(self, which, mask, ids, force=None, dforce=None, scratch=None):
+    def tail_ptrs(self, which, mask, ids, force=None, dforce=None, scratch=None, omf=None, domf=None):
         """The pointers after the pdf arrays in the argument list of ``lbm_fwd`` / ``lbm_adj`` / ``lbm_adj_fix``: mask,
-        ids, then force[, dforce], then the second pass's scratch array (None: a slot patched per launch). Torch
-        tensors, or numpy arrays on the C path."""
+        ids, then force[, dforce], then the ω field[, its adjoint], then the second pass's scratch array (None: a slot
+        patched per launch). Torch tensors, or numpy arrays on the C path."""
         ptrs = (_ptr(mask), _ptr(ids))
         if force is not None:
             ptrs += (_ptr(force),) + ((_ptr(dforce),) if which == 'adj' else ())
+        if omf is not None:
+            ptrs += (_ptr(omf),) + ((_ptr(domf),) if which == 'adj' else ())
         if which == 'adj' and self.link_pass:
             ptrs += (_ptr(scratch),)
         return ptrs
@@ -227,12 +232,11 @@ class LatticeKernels:
             addr = 'ptr'
         return idx, addr
 
-    def _launch_mode(self, tensors, force=None, dforce=None):
-        """``(idx, addr)`` of a ``plan()`` launch: ``_mode`` of the pdf tensors; the force (and its adjoint) is
-        read through plain pointers with IDX offsets, so a far-reaching force field widens ``idx`` alone."""
+    def _launch_mode(self, tensors, force=None, dforce=None, omf=None, domf=None):
+        """``(idx, addr)`` of a ``plan()`` launch: ``_mode`` of the pdf tensors; the force and the ω field (and
+        their adjoints) are read through plain pointers with IDX offsets, so a far-reaching one widens ``idx`` alone."""
         idx, addr = self._mode(tensors)
-        if force is not None and max(self._reach(force), self._reach(dforce) if dforce is not None else 0) \
-                >= 2 ** 31 - 1:
+        if max([self._reach(t) for t in (force, dforce, omf, domf) if t is not None], default=0) >= 2 ** 31 - 1:
             idx = 'long long'
         return idx, addr
 
@@ -252,10 +256,37 @@ class LatticeKernels:
             return fmt, None
         return fmt + 'QQ' + code * 4, len(fmt)
 
-    def _strides(self, arrays, force):
-        """The strides after the extents in every kernel's argument list: of each pdf array, then of the force field."""
-        return [n for a in list(arrays) + ([force] if force is not None else [])
-                for n in lattice_strides(a, self.stencil.D)]
+    def _strides(self, arrays, force, omf=None):
+        """The strides after the extents in every kernel's argument list: of each pdf array, then of the force field,
+        then ``(s_z, s_y, s_x)`` of the ω field (2-D: ``s_z`` = 0)."""
+        st = [n for a in list(arrays) + ([force] if force is not None else [])
+              for n in lattice_strides(a, self.stencil.D)]
+        if omf is not None:
+            sw = [int(v) for v in (omf.stride() if hasattr(omf, 'stride') and callable(omf.stride) else
+                                   [v // omf.itemsize for v in omf.strides])]
+            st += [0] * (3 - len(sw)) + sw
+        return st
+
+    def _omega_check(self, shape, omf, domf, which, xp_tensor=True):
+        """The per-cell relaxation rate (and, for the adjoint, its accumulated adjoint): ``[*domain]`` of the pdf
+        dtype, ``domf`` with the strides of ``omf``; none without an ω field."""
+        D = self.stencil.D
+        need = [omf] + ([domf] if which == 'adj' else [])
+        if not self.omega_field:
+            if omf is not None or domf is not None:
+                raise ValueError('these lattice kernels take no relaxation-rate field')
+            return
+        if any(t is None for t in need):
+            raise ValueError('the ω-field lattice kernels need the relaxation-rate field'
+                             f'{" and its adjoint" if which == "adj" else ""}')
+        for t in need:
+            if tuple(t.shape) != tuple(shape[:D]):
+                raise ValueError(f'relaxation-rate field of shape {tuple(t.shape)}: expected {tuple(shape[:D])}')
+            if (t.dtype != self.dtype) if not xp_tensor else (str(t.dtype).split('.')[-1] != self.dtype.name):
+                raise ValueError(f'relaxation-rate field dtype {t.dtype}: expected {self.dtype}')
+        if which == 'adj' and tuple(domf.stride() if xp_tensor else domf.strides) != \
+                tuple(omf.stride() if xp_tensor else omf.strides):
+            raise ValueError('the relaxation-rate adjoint must have the strides of the relaxation-rate field')
 
     def _force_check(self, shape, force, dforce, which, xp_tensor=True):
         """The per-cell force (and, for the adjoint, its accumulated adjoint): ``[*domain, D]`` of the pdf dtype,
@@ -277,7 +308,7 @@ class LatticeKernels:
                 tuple(force.stride() if xp_tensor else force.strides):
             raise ValueError('the force adjoint must have the strides of the force')
 
-    def plan(self, which, tensors, mask, omega, ids=None, force=None, dforce=None, fix=None):
+    def plan(self, which, tensors, mask, omega, ids=None, force=None, dforce=None, fix=None, omf=None, domf=None):
         """The launch of ``which`` ('fwd' / 'adj') on tensors of these shapes, strides, dtype and device (with or
         without walls): a ``LaunchPlan`` whose pointer slots and relaxation rate are patched per launch — the
         time-step op launches T of them per apply. ω is not part of the key (a trained or scheduled rate reuses the
@@ -286,20 +317,24 @@ class LatticeKernels:
         key = (which, mask is not None) + tuple((tuple(t.shape), tuple(t.stride()), t.dtype, t.device)
                                                 for t in tensors) + \
             ((tuple(force.shape), tuple(force.stride())) if force is not None else ()) + \
+            (('omf', tuple(omf.shape), tuple(omf.stride())) if omf is not None else ()) + \
             ((fix[0].data_ptr(), int(fix[0].numel())) if fix is not None else ())
         plan = self._plans.get(key)
         if plan is not None:
             return plan
         self._force_check(tuple(tensors[0].shape), force, dforce, which)
+        self._omega_check(tuple(tensors[0].shape), omf, domf, which)
         self._check(tensors, mask, ids)
-        strides = self._strides(tensors, force)
-        idx, addr = self._launch_mode(tensors, force, dforce)
+        if any(t is not None and (not t.is_cuda or t.device != tensors[0].device) for t in (omf, domf)):
+            raise ValueError('the relaxation-rate field must be on the pdf tensors\' device')
+        strides = self._strides(tensors, force, omf)
+        idx, addr = self._launch_mode(tensors, force, dforce, omf, domf)
         dev = tensors[0].device.index
         fn = self._gpu_fn(which + ('_fix' if fix is not None else ''), idx, addr, dev)
         Z, Y, X = self._extent(tensors[0])
         nblocks = self._blocks(X, Y, Z) if fix is None else -(-int(fix[0].numel()) // FIX_BLOCK)
         reach = [self._reach(t) * t.element_size() for t in tensors]
-        ptrs = [t.data_ptr() for t in tensors] + list(self.tail_ptrs(which, mask, ids, force, dforce))
+        ptrs = [t.data_ptr() for t in tensors] + list(self.tail_ptrs(which, mask, ids, force, dforce, None, omf, domf))
         fmt, om_i = self._arg_format(idx, len(tensors), len(ptrs), len(strides), fix is not None)
         vals = [*ptrs, Z, Y, X, *strides, *reach, float(omega)]
         if fix is not None:
@@ -311,16 +346,17 @@ class LatticeKernels:
             plan.block = FIX_BLOCK
         return plan
 
-    def fix_launch(self, which, tensors, mask, omega, ids, force, dforce, cells, stream):
+    def fix_launch(self, which, tensors, mask, omega, ids, force, dforce, cells, stream, omf=None, domf=None):
         """The fix-up launch after a main adjoint launch on ``tensors`` (HIP with link programs; nothing for the
         forward, which runs them inline, or when no cell is listed): the listed cells' adjoint with their programs'
         Jacobian terms, added atomically into the entries the main launch left zeroed (no second fix-up launch)."""
         if which != 'adj' or self.programs is None or self.target != 'gpu' or cells is None or \
                 int(cells.numel()) == 0:
             return
-        plan = self.plan(which, tensors, mask, omega, ids, force, dforce, fix=(cells,))
+        plan = self.plan(which, tensors, mask, omega, ids, force, dforce, fix=(cells,), omf=omf, domf=domf)
         rho = self.rho_buffer(tensors[0]) if self.link_pass else None
-        plan(tuple(t.data_ptr() for t in tensors) + self.tail_ptrs(which, mask, ids, force, dforce, rho), stream, omega)
+        plan(tuple(t.data_ptr() for t in tensors) + self.tail_ptrs(which, mask, ids, force, dforce, rho, omf, domf),
+             stream, omega)
 
     def _scratch_shape(self, domain):
         """Of the second adjoint pass's scratch array: one value per cell (density-weighted links); with inline link
@@ -364,26 +400,28 @@ class LatticeKernels:
             plan.extra = _offset(fmt, extra_i)            # the src / ids slots, patched per launch
         return plan
 
-    def forward(self, src, dst, omega, mask=None, stream=None, ids=None, force=None, cells=None):
+    def forward(self, src, dst, omega, mask=None, stream=None, ids=None, force=None, cells=None, omf=None):
         """``dst = stream-pull-collide(src)`` (torch tensors ``[*domain, q]``, any strides; ``force``: the per-cell
-        force ``[*domain, D]`` of force-field kernels)."""
+        force ``[*domain, D]`` of force-field kernels; ``omf``: the per-cell relaxation rate ``[*domain]`` of ω-field
+        kernels, which ignore ``omega``)."""
         if self.target != 'gpu':
-            return self._cpu('fwd', [src, dst], omega, mask, ids, force)
+            return self._cpu('fwd', [src, dst], omega, mask, ids, force, omf=omf)
         st = _stream(stream, src)
-        self.plan('fwd', [src, dst], mask, omega, ids, force)(
-            (src.data_ptr(), dst.data_ptr()) + self.tail_ptrs('fwd', mask, ids, force), st, omega)
+        self.plan('fwd', [src, dst], mask, omega, ids, force, omf=omf)(
+            (src.data_ptr(), dst.data_ptr()) + self.tail_ptrs('fwd', mask, ids, force, omf=omf), st, omega)
 
-    def adjoint(self, src, g, out, omega, mask=None, stream=None, ids=None, force=None, dforce=None, cells=None):
+    def adjoint(self, src, g, out, omega, mask=None, stream=None, ids=None, force=None, dforce=None, cells=None,
+                omf=None, domf=None):
         """``out = (∂ step / ∂ src)ᵀ g`` at the state ``src``; force-field kernels also ADD ``(∂ step / ∂ F)ᵀ g`` to
-        ``dforce``."""
+        ``dforce``, ω-field kernels ``(∂ step / ∂ ω)ᵀ g`` to ``domf``."""
         if self.target != 'gpu':
-            return self._cpu('adj', [src, g, out], omega, mask, ids, force, dforce)
+            return self._cpu('adj', [src, g, out], omega, mask, ids, force, dforce, omf, domf)
         st = _stream(stream, src)
         rho = self.rho_buffer(src) if self.link_pass else None
-        self.plan('adj', [src, g, out], mask, omega, ids, force, dforce)(
-            (src.data_ptr(), g.data_ptr(), out.data_ptr()) + self.tail_ptrs('adj', mask, ids, force, dforce, rho),
-            st, omega)
-        self.fix_launch('adj', [src, g, out], mask, omega, ids, force, dforce, cells, st)
+        self.plan('adj', [src, g, out], mask, omega, ids, force, dforce, omf=omf, domf=domf)(
+            (src.data_ptr(), g.data_ptr(), out.data_ptr()) +
+            self.tail_ptrs('adj', mask, ids, force, dforce, rho, omf, domf), st, omega)
+        self.fix_launch('adj', [src, g, out], mask, omega, ids, force, dforce, cells, st, omf, domf)
         if rho is not None:
             self.rho_pass(out, mask, rho, src, ids, st)
 
@@ -412,7 +450,7 @@ class LatticeKernels:
             fn = self._fns[which] = compile_c(self.source(), f'lbm_{which}', openmp=True)
         return fn
 
-    def _cpu(self, which, arrays, omega, mask, ids=None, force=None, dforce=None):
+    def _cpu(self, which, arrays, omega, mask, ids=None, force=None, dforce=None, omf=None, domf=None):
         arrays = [np.asarray(a) for a in arrays]
         for a in arrays:
             if a.dtype != self.dtype:
@@ -422,11 +460,12 @@ class LatticeKernels:
         idv = None if ids is None else np.ascontiguousarray(ids, dtype=np.uint8)
         shape = self._check_domain(arrays, m, idv)
         self._force_check(shape, force, dforce, which, xp_tensor=False)
+        self._omega_check(shape, omf, domf, which, xp_tensor=False)
         fn = self._cpu_fn(which)
-        strides = self._strides(arrays, force)
+        strides = self._strides(arrays, force, omf)
         # the second pass's scratch (both passes in one call)
         rho = np.empty(self._scratch_shape(shape[:D]), self.dtype) if which == 'adj' and self.link_pass else None
-        ptrs = [a.ctypes.data for a in arrays] + list(self.tail_ptrs(which, m, idv, force, dforce, rho))
+        ptrs = [a.ctypes.data for a in arrays] + list(self.tail_ptrs(which, m, idv, force, dforce, rho, omf, domf))
         ext = list(shape[:D]) if D == 3 else [1] + list(shape[:D])
         P = (ctypes.c_void_p * len(ptrs))(*ptrs)
         N = (ctypes.c_longlong * 3)(*ext)

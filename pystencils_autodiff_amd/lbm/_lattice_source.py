@@ -2,9 +2,9 @@
 
 ``LatticeSource`` says what to print — the lattice (stencil, collision, force, walls and their links), the target
 (HIP / C), the index type, the addressing mode and the adjoint mode — and ``emit`` prints it: the forward cell
-(``lbm_fwd_cell``), the adjoint cell (``lbm_adj_cell``: prologue, moment-like sums, force adjoint, scatter), the
-adjoint's second pass (``lbm_adj_rho_cell``) and the entry points that call them for every cell: HIP grid kernels,
-the HIP fix-up kernel over a cell list, or C loop nests.
+(``lbm_fwd_cell``), the adjoint cell (``lbm_adj_cell``: prologue, moment-like sums, force adjoint, ω-field adjoint,
+scatter), the adjoint's second pass (``lbm_adj_rho_cell``) and the entry points that call them for every cell: HIP
+grid kernels, the HIP fix-up kernel over a cell list, or C loop nests.
 
 Adjoint modes. ``programs`` gives per wall id None or the boundary's ``link_program`` (links of the cell's own pdfs the
 fused form does not take, ``boundaries.link_program``; their table rows are zeros): the forward evaluates the link
@@ -54,6 +54,9 @@ class LatticeSource:
     magic number, computed per launch from the ω argument) or ``('rate', ω₋)`` (a constant).
     ``mrt``: the MRT method's relaxation matrix ``A = ω P_ω + C`` (``(P_ω, C)``, Q×Q numbers, ``_method.
     mrt_relaxation_matrices`` summed over the groups relaxing with the ω argument / with constant rates).
+    ``omega_field``: the relaxation rate ω is a per-cell scalar field ``[*domain]`` read by strides (the scalar ``omega``
+    argument is then ignored) and the adjoint ACCUMULATES ``dω(x) = Σ_i g_i ∂dst_i/∂ω`` into ``domega``
+    (``_Printer.omega_adjoint``).
     ``target`` 'hip' / 'c'. ``idx``: the type of every stride and element offset (``long long`` once an array, or the
     force field, reaches 2³¹ − 1 elements). ``addr`` 'buf' / 'ptr' (``_Addressing``). ``mode`` 'inline' / 'main' /
     'fix' (the module docstring).
@@ -75,6 +78,7 @@ class LatticeSource:
     idx: str = 'i64'
     addr: str = 'ptr'
     mode: str = 'inline'
+    omega_field: bool = False
 
     def __post_init__(self):
         links, programs = self.links, self.programs
@@ -85,6 +89,7 @@ class LatticeSource:
         self.keys = sorted({_key(d) for d in self.dirs})          # one name per distinct neighbour cell x − c
         self.fm = None if self.force_model is None else str(self.force_model).lower()
         self.ff = bool(self.fm) and bool(self.force_field)
+        self.of = bool(self.omega_field)
         # Guo with TRT / MRT: the force term (prefactor 1 − ω/2 with the shear rate ω, as lbmpy's Guo model) is not
         # relaxed by the collision matrix, so its adjoint sums run over g while the equilibrium's run over h
         self.gsplit = self.fm == 'guo' and (self.trt is not None or self.mrt is not None)
@@ -262,20 +267,26 @@ class _Printer:
             P += ['const unsigned* __restrict__ nbmask', 'const unsigned char* __restrict__ wallid'] + more
             P += ['const int Z', 'const int Y', 'const int X'] + [f'const IDX {p}_{a}' for p in pdfs for a in 'qzyx']
             P += [f'const IDX f_{a}' for a in 'czyx'] if s.ff else []
-            return P + [f'const long long {p}_bytes' for p in pdfs] + [f'const {self.ct} omega']
+            P += [f'const IDX w_{a}' for a in 'zyx'] if s.of else []
+            # (with an ω field the scalar rate is not what the collision reads: the cell loads ``omega``)
+            return P + [f'const long long {p}_bytes' for p in pdfs] + [f'const {self.ct} omega{"_s" if s.of else ""}']
         force = ['const T* __restrict__ force'] if s.ff else []
+        omf = ['const T* __restrict__ omf'] if s.of else []
         rho = ['T* __restrict__ out', 'const unsigned* __restrict__ nbmask', 'const T* __restrict__ rho_adj',
                'const int Z', 'const int Y', 'const int X'] + [f'const IDX o_{a}' for a in 'qzyx']
         if s.inl:
             # the programs' Jacobians read the cell's own pdfs and the neighbours' wall ids
             rho += ['const T* __restrict__ src', 'const unsigned char* __restrict__ wallid'] + \
                 [f'const IDX s_{a}' for a in 'qzyx']
-        P = dict(fwd=params('sd', force), adj_rho=rho,
+        P = dict(fwd=params('sd', force + omf), adj_rho=rho,
                  adj=params('sgo', force + (['T* __restrict__ dforce'] if s.ff else []) +
+                            omf + (['T* __restrict__ domega'] if s.of else []) +
                             (['T* __restrict__ rho_adj'] if s.two else [])))
         self.sig = {k: ', '.join(v) for k, v in P.items()}
         self.args = {k: ', '.join(p.split()[-1] for p in v) for k, v in P.items()}
         self.fstr_unused = '(void)f_z; ' if s.ff and self.D == 2 else ''
+        if s.of:
+            self.fstr_unused += '(void)omega_s; ' + ('(void)w_z; ' if self.D == 2 else '')
 
     def module(self):
         s, L = self.s, []
@@ -399,6 +410,14 @@ class _Printer:
             if any(self.dirs[i]):
                 L.append(f'  const {ct} cF{i} = {self.signed_sum(i, "F")};')
 
+    def omega_load(self, L):
+        """The cell's relaxation rate (``omega_field``): every use of ``omega`` after it — the collision, the TRT
+        rates, Guo's 1 − ω/2, MRT's ω P_ω — reads this local."""
+        if not self.s.of:
+            return
+        L.append('  const IDX wc = ' + ' + '.join(f'(IDX){a} * w_{a}' for a in self.axes) + ';')
+        L.append(f'  const {self.ct} omega = ({self.ct})omf[wc];')
+
     def pull_loads(self, L, progs=True, hoisted=False):
         """``f_i``: the pulled pdfs of the cell — ``src_i(x − c_i)``, or the link of the wall cell there (bounce-back
         ``src_ī(x)``, its table row ``α f + β (+ βρ ρ)``, or its program).
@@ -509,6 +528,7 @@ class _Printer:
             self.obstacle_copy(L, 'd', dcoff, lambda i: A.load('s', i, f'so_{self.centre}'))
 
         self.force_loads(L)
+        self.omega_load(L)
         self.cell_density(L)
         self.pull_loads(L)
         self.moments(L)
@@ -558,12 +578,14 @@ class _Printer:
         for i in range(self.Q):
             L.append(f'  const {ct} g{i} = {A.load("g", i, gcoff)};')
         self.force_loads(L)
+        self.omega_load(L)
         self.cell_density(L)
         listed = s.fix and bool(s.gq_all)
         if listed:
             self.fix_loads(L)
         self.pull_loads(L, self.adj_progs, hoisted=listed and s.walls)
         self.moments(L)
+        self.omega_adjoint_pdfs(L)
         if s.rho_links:
             L.append(f'  {ct} Rr = 0;')             # Σ_j βρ_j v_j over the cell's density-weighted links
         gown = s.g_own if s.fix else []
@@ -571,6 +593,7 @@ class _Printer:
             L.append(f'  {ct} ' + ', '.join(f'G{q} = 0' for q in gown) + ';')      # Σ_j J_jq v_j (link programs)
         self.adjoint_sums(L)
         self.force_adjoint(L)
+        self.omega_adjoint(L)
         if s.compressible:
             L.append(f'  const {ct} Bu = ' + ' + '.join(f'B{a} * u{a}' for a in range(self.D)) + ';')
         for j in range(self.Q):
@@ -727,6 +750,63 @@ class _Printer:
                 sc = '' if s.gsplit else 'omega * '
                 val = f'kg * Bf{a} + ({ct})0.5 * {sc}B{a}' + (' * irho' if s.compressible else '')
             L.append(f'  dforce[(IDX){a} * f_c + fc] += {val};')
+
+    def omega_weight(self, k):
+        """``q_k`` of ``dω = −Σ_k q_k n_k`` (``omega_adjoint``; None where it is the constant 0)."""
+        s = self.s
+        if s.trt is not None and self.inv[k] != k:
+            return f'(tap * g{k} + tbp * g{self.inv[k]})'
+        if s.mrt is not None:
+            pw = self.mat_row(s.mrt[0], 'g', k, True)
+            return f'({pw})' if pw else None
+        return f'g{k}'
+
+    def omega_adjoint_pdfs(self, L):
+        """``omega_field``: the part of ``dω`` that reads the pulled pdfs, ``dom = −Σ_k q_k f_k`` — taken right after
+        the moments, so that no ``f_k`` stays live through the adjoint's sums (``omega_adjoint`` has the formulas)."""
+        s, ct = self.s, self.ct
+        if not s.of:
+            return
+        if s.trt is not None:
+            if s.trt[0] == 'magic':
+                lam = self.c_(s.trt[1])
+                L.append(f'  const {ct} wden = ({ct})4 * {lam} * omega + ({ct})2 - omega;')
+                L.append(f'  const {ct} wodp = -({ct})16 * {lam} / (wden * wden);')
+            else:
+                L.append(f'  const {ct} wodp = 0;')
+            L.append(f'  const {ct} tap = ({ct})0.5 * (({ct})1 + wodp), tbp = ({ct})0.5 * (({ct})1 - wodp);')
+        L.append(f'  {ct} dom = 0;')
+        for k in range(self.Q):
+            if self.omega_weight(k):
+                L.append(f'  dom -= {self.omega_weight(k)} * f{k};')
+
+    def omega_adjoint(self, L):
+        """``omega_field``: the cell's ``dω(x) = Σ_i g_i ∂dst_i/∂ω``, ACCUMULATED into ``domega`` (the strides of the ω
+        field; every cell by one thread of one adjoint launch per step — a listed cell by the fix-up launch, which
+        the main launch's prologue left it to — so the T steps sum into one zeroed array without atomics).
+        With ``n = f − feq``: ``dω = −Σ_k q_k n_k = −Σ_k q_k f_k`` (``omega_adjoint_pdfs``) ``+ Σ_k q_k feq_k`` (here:
+        the equilibria recomputed from ρ, u — no load, and no pdf held in a register for it), a cancelling sum.
+
+        SRT ``q = g``: ``dω = −Σ_i g_i n_i``. TRT ``dst_i = f_i − a n_i − b n_ī``: ``q_k = a′ g_k + b′ g_k̄``, ``a′ =
+        (1 + ω₋′)/2``, ``b′ = (1 − ω₋′)/2``, ``ω₋′ = −16Λ / (4Λω + 2 − ω)²`` (magic number) or 0 (a constant odd rate);
+        the rest population ``q_0 = g_0``. MRT ``dst = f − (ω P_ω + C) n``: ``q = P_ωᵀ g``. Guo's term
+        ``w_i (1 − ω/2) T_i``, ``T_i = 3 (c_i − u)·F + 9 (c_i·u)(c_i·F)``, adds ``−½ Σ_i g_i w_i T_i``."""
+        s, ct, w = self.s, self.ct, self.w
+        if not s.of:
+            return
+        if s.fm == 'guo':
+            L.append(f'  {ct} domF = 0;')                 # Σ_i g_i w_i T_i
+        for i in range(self.Q):
+            self.cu_poly(L, i)
+            if self.omega_weight(i):
+                L.append(f'    dom += {self.omega_weight(i)} * ({self.feq(i)});')
+            if s.fm == 'guo':
+                L.append(f'    domF += g{i} * {self.c_(w[i])} * (({ct})3 * ({self.cFi(i) or self.c_(0)} - uF)'
+                         + (f' + {self.cFi(i, 9)} * cu' if self.cFi(i) else '') + ');')
+            L.append('  }')
+        if s.fm == 'guo':
+            L.append(f'  dom -= ({ct})0.5 * domF;')
+        L.append('  domega[wc] += (T)dom;')
 
     def scatter(self, L, j):
         """``v_j``, stored to the cell the forward pulled ``f_j`` from — ``(x − c_j, j)``, or ``(x, ī)`` for a bounced
@@ -933,7 +1013,7 @@ class _Printer:
             adj, n = k == 'adj', len(pdfs)
             L.append(f'void lbm_{k}(void** P, const i64* N, const i64* S, const i64* B_, const double* Dv)\n{{')
             L.append('  (void)B_; const int Z = (int)N[0], Y = (int)N[1], X = (int)N[2];')
-            L.append(f'  const {ct} omega = ({ct})Dv[0];')
+            L.append(f'  const {ct} omega{"_s" if s.of else ""} = ({ct})Dv[0];')
             ptrs = [('const T*', ARRAYS[p]) for p in pdfs[:-1]] + [('T*', ARRAYS[pdfs[-1]])] + \
                 [('const unsigned*', 'nbmask'), ('const unsigned char*', 'wallid')]
             L.append('  ' + ' '.join(f'{ty} {nm} = ({ty})P[{i}];' for i, (ty, nm) in enumerate(ptrs)))
@@ -942,8 +1022,13 @@ class _Printer:
             if s.ff:
                 L.append(f'  const T* force = (const T*)P[{n + 2}];' + (f' T* dforce = (T*)P[{n + 3}];' if adj else ''))
                 L.append('  const IDX ' + ', '.join(f'f_{a} = S[{4 * n + j}]' for j, a in enumerate('czyx')) + ';')
+            nf = n + 2 + ((2 if adj else 1) if s.ff else 0)       # pointers before the ω field's
+            if s.of:
+                L.append(f'  const T* omf = (const T*)P[{nf}];' + (f' T* domega = (T*)P[{nf + 1}];' if adj else ''))
+                L.append('  const IDX ' + ', '.join(f'w_{a} = S[{4 * n + (4 if s.ff else 0) + j}]'
+                                                    for j, a in enumerate('zyx')) + ';')
             if adj and s.two:
-                L.append(f'  T* rho_adj = (T*)P[{n + (4 if s.ff else 2)}];')
+                L.append(f'  T* rho_adj = (T*)P[{n + (4 if s.ff else 2) + (2 if s.of else 0)}];')
             L.append('  const long long ' + ', '.join(f'{p}_bytes = 0' for p in pdfs) + ';')
             for cellfn in (k, 'adj_rho') if adj and s.two else (k,):
                 # (the density pass after every cell's scatter: the C target runs both passes in one call)

@@ -236,13 +236,15 @@ def run_slab(name, builder, shape, dtype, full_cells, steps=20, warmup=3):
 
 
 def run_lbm(name, stencil, shape, dtype, T=10, reps=5, compressible=False, walls=False, force_model=None,
-            force_field=False, method='srt'):
+            force_field=False, method='srt', omega_field=False):
     """Lattice Boltzmann time-step op (lbm.AutoDiffLatticeBoltzmannStep.create_timestep_op): T forward steps
     and the T adjoint steps, HIP events around Op.apply and backward (back-to-back applies). MLUPS = cells · T / time; algorithmic
     bytes per cell and step: forward 2q·s (read src, write dst), adjoint 3q·s (read diffdst and the recorded
     src, write diffsrc), s = element size; the ghost sync, state records and adjoint border fills are extra.
     ``force_field``: a per-cell force (a D-component fzyx field, an input of the op): + D·s per cell and step forward
-    (the force read), + 3·D·s adjoint (the force read, its accumulated adjoint read and written)."""
+    (the force read), + 3·D·s adjoint (the force read, its accumulated adjoint read and written).
+    ``omega_field``: the relaxation rate per cell (a scalar field, an input of the op): + s forward (the ω read), + 3·s
+    adjoint (the ω read, its accumulated adjoint read and written) — (2q + 1)·s and (3q + 3)·s."""
     import sympy as sp
     import torch
 
@@ -254,9 +256,12 @@ def run_lbm(name, stencil, shape, dtype, T=10, reps=5, compressible=False, walls
     if force_model and force_field:
         force = ps.fields(f"F({D}): {dts}[{D}D]", layout='fzyx')
     mk = dict(method='mrt', relaxation_rates=[sp.Symbol('omega'), 1.1, 0.9, 1.2]) if method == 'mrt' else {}
+    if omega_field:
+        mk['relaxation_rate'] = ps.fields(f"omega_f: {dts}[{D}D]").center
     rule = lbm.create_lb_update_rule(stencil, compressible=compressible, data_type=dts, force_model=force_model,
                                      force=force, **mk)
-    step = lbm.AutoDiffLatticeBoltzmannStep(rule, domain_size=shape, relaxation_rate=1.5, target='gpu')
+    step = lbm.AutoDiffLatticeBoltzmannStep(rule, domain_size=shape, relaxation_rate=None if omega_field else 1.5,
+                                            target='gpu')
     if walls == 'freeslip':
         # a slip channel: free-slip (specular) walls on the first and last rows of axis 1 (neighbour links)
         n = (0, 1) + (0,) * (D - 2)
@@ -287,10 +292,16 @@ def run_lbm(name, stencil, shape, dtype, T=10, reps=5, compressible=False, walls
         Fv = torch.empty([D] + list(shape), device='cuda', dtype=dtype).permute(*range(1, D + 1), 0)
         Fv.copy_(1e-5 * (torch.rand(tuple(shape) + (D,), generator=g, device='cuda', dtype=dtype) - 0.5))
         extra = (Fv.requires_grad_(True),)
+    if omega_field:
+        # (extras in name order: the force field F before omega_f)
+        Wv = 1.5 + 0.4 * (torch.rand(tuple(shape), generator=g, device='cuda', dtype=dtype) - 0.5)
+        extra += (Wv.requires_grad_(True),)
 
     def one():
         Op.apply(x, *extra).backward(gr)
         x.grad = None
+        for e in extra:
+            e.grad = None
     settle(one)
     # back-to-back applies as run() times the stencil configs (the queue stays ahead of the GPU: event times are
     # the op's GPU time, not the host latency to its first launch after an idle GPU)
@@ -303,6 +314,8 @@ def run_lbm(name, stencil, shape, dtype, T=10, reps=5, compressible=False, walls
         out.backward(gr)
         e2.record()
         x.grad = None
+        for e in extra:
+            e.grad = None                   # (no gradient accumulation kernel inside the next backward's window)
         if i >= 2:
             ev.append((e0, e1, e2))
     torch.cuda.synchronize()
@@ -319,10 +332,14 @@ def run_lbm(name, stencil, shape, dtype, T=10, reps=5, compressible=False, walls
            'walls': walls if isinstance(walls, str) else bool(walls),
            'fwd_mlups': round(cells * T / (f_ms * 1e-3) / 1e6, 1), 'bwd_mlups': round(cells * T / (b_ms * 1e-3) / 1e6, 1),
            'fwd_ms': round(f_ms, 4), 'bwd_ms': round(b_ms, 4),
-           'fwd_GBps': round((2 * q + (D if force_field else 0)) * es * cells * T / (f_ms * 1e-3) / 1e9, 1),
-           'bwd_GBps': round((3 * q + (3 * D if force_field else 0)) * es * cells * T / (b_ms * 1e-3) / 1e9, 1),
+           'fwd_GBps': round((2 * q + (D if force_field else 0) + int(omega_field)) * es * cells * T
+                             / (f_ms * 1e-3) / 1e9, 1),
+           'bwd_GBps': round((3 * q + (3 * D if force_field else 0) + 3 * int(omega_field)) * es * cells * T
+                             / (b_ms * 1e-3) / 1e9, 1),
            'force': (f'{force_model}, per-cell field' if force_field else force_model) if force_model else None,
            'method': method}
+    if omega_field:
+        res['omega'] = 'per-cell field'
     res['fwd_frac'] = round(res['fwd_GBps'] / PEAK, 4)
     res['bwd_frac'] = round(res['bwd_GBps'] / PEAK, 4)
     print(json.dumps(res))
@@ -414,12 +431,16 @@ def main():
             ('lbm_d2q9_f32_2048^2_freeslip', 'D2Q9', (2048, 2048), torch.float32, 'freeslip'),
             ('lbm_d3q19_f32_192^3_freeslip', 'D3Q19', (192, 192, 192), torch.float32, 'freeslip'),
             ('lbm_d2q9_f32_2048^2_mrt', 'D2Q9', (2048, 2048), torch.float32, False, 'mrt'),
-            ('lbm_d3q19_f32_192^3_mrt', 'D3Q19', (192, 192, 192), torch.float32, False, 'mrt')]
-    for name, stencil, shape, dt, walls, *method in lbms:
+            ('lbm_d3q19_f32_192^3_mrt', 'D3Q19', (192, 192, 192), torch.float32, False, 'mrt'),
+            # ω read per cell from a scalar field, its adjoint accumulated (next to their scalar-ω twins above)
+            ('lbm_d2q9_f32_2048^2_omega_field', 'D2Q9', (2048, 2048), torch.float32, False, 'srt', True),
+            ('lbm_d3q19_f32_192^3_omega_field', 'D3Q19', (192, 192, 192), torch.float32, False, 'srt', True)]
+    for name, stencil, shape, dt, walls, *more in lbms:
         if only and name not in only:
             continue
         for _ in range(repeat):
-            run_lbm(name, stencil, shape, dt, walls=walls, method=method[0] if method else 'srt')
+            run_lbm(name, stencil, shape, dt, walls=walls, method=more[0] if more else 'srt',
+                    omega_field=len(more) > 1 and more[1])
 
 
 if __name__ == '__main__':
