@@ -6,7 +6,8 @@ then ``kernel<<<grid, block>>>`` from ``indexing.call_parameters``,
 ``printer.py:88-108``). Calling convention kept: ``kernel(x=..., y=..., z=..., a=5.)``
 with every field tensor and scalar passed by name, outputs written in place.
 Launches go to torch's current HIP stream (the reference used the legacy
-default stream, ``printer.py:106``).
+default stream, ``printer.py:106``). Which march kernel a launch gets is decided in ``march_plan`` (host code
+without torch or a device, pinned by ``tests/test_march_plan.py``); this module compiles, sizes the grid and packs.
 """
 import math
 import os
@@ -14,396 +15,13 @@ import os
 import numpy as np
 
 from . import hip_runtime as rt
-from .hip_band import band_choice, band_esize, band_geometry, band_plans, emit_band
-from .hip_emitter import (MarchConfig, emit_generic, emit_march, emit_pointwise, emit_zsum, march_geometry, pair_ok,
-                          storage_ctype, ws_geometry, zsum_plan)
+from .hip_band import band_geometry, emit_band
+from .hip_emitter import (MarchConfig, emit_generic, emit_march, emit_pointwise, emit_zsum, march_geometry, ncomp,
+                          ws_geometry, zsum_plan)
+from .march_plan import (PROBE_KEYS, PROBE_KNOBS, TILE_KEYS, align_class as _align_class,  # noqa: F401 (re-exports)
+                         default_march_config, is_pair as _is_pair, march_extents, resolve_march, ws_fallback_config)
 
 __all__ = ['HipStencilKernel', 'default_march_config']
-
-
-# row-band defaults, settled A/B rounds through the op (fn.apply + backward, same process;
-# scripts/probes/op_band_ab.py, profiles/r03_op_band_ab*.log): box stencils (27 taps) 48-plane chunks without the
-# trimmed chunk-edge planes (fwd+bwd 1024³ 1.707 vs 1.809 ms zsum, trimmed 24-plane chunks 2.01; 768³ 0.731 vs
-# 0.762), star stencils 8-plane chunks (fp16 7-point 1024³ 1.461 vs 1.538, 768³ 0.635 vs 0.682). Launches of fewer
-# than BAND_MIN_WG workgroups (z-slabs of a few planes) keep the zsum ring.
-BAND_ZC_BOX, BAND_ZC_STAR = 48, 8
-# round 4 (profiles/r04_op_band_ab1.log, same process, fwd+bwd through the op): the chunk's first two planes peeled
-# without the taps of outputs before it (BTRIM=1) — 27-point 768³ 0.744 vs 0.768 ms, 1024³ 16-row bands 1.718 vs 1.744
-# (and 1.679 with 32-plane chunks), fp16 7-point 768³ 0.602 vs 0.626
-BAND_ZC_BOX16 = 32
-# round 4 (profiles/r04_op_band_ab3.log .. _ab5.log): both chunk ends peeled at a compile-time chunk length (BTRIM=3)
-# — 27-point 768³ 0.715 vs 0.724 ms (BTRIM=1), 1024³ 1.617 vs 1.640, fp16 7-point 768³ 0.594 vs 0.595-0.633
-BAND_TRIM_DEFAULT = 3
-# box-stencil chunk length: the longest of BAND_ZC_BOX_LADDER that still gives BAND_ROUND_WG workgroups (one
-# round of three per CU; profiles/r04_op_zc_sweep.log): 27-point 512³ 32 planes 0.209 ms vs 16 0.243, 8 0.235;
-# 256³ 8 planes 0.028 vs 11 0.036, 16 0.045; a 96×768² slab 12 planes 0.091 vs 8 0.095, 24 0.109
-BAND_ZC_BOX_LADDER = (48, 32, 24, 16, 12, 8)
-BAND_ROUND_WG = 768
-BAND_MIN_WG = 768
-# star stencils: 8-plane chunks, but 64-plane chunks on rows of <= 512 elements when that still gives >= 512
-# workgroups (profiles/r04_op_zc_sweep.log, _ab6.log): fp16 7-point 512³ 0.184 vs 0.197 ms, 510³ 0.204 vs 0.229;
-# 768³ keeps 8 (0.629 vs 0.675 at 96 planes, 0.699 at 64), 256³ too (0.024 vs 0.038 at 32)
-BAND_ZC_STAR_LONG, BAND_STAR_LONG_MAX_X, BAND_STAR_LONG_MIN_WG = 64, 512, 512
-# fp32 storage (4 cells per 16-byte chunk): 4-row bands measured slower through the op (7-point 512³ 0.387 vs
-# 0.373 ms, 768³ 1.325 vs 1.261); 8-row bands of 4 rows per lane (4 compute waves, 60 KB of LDS) faster for star
-# stencils on rows of <= 512 on every box (profiles/r04_op_f7_ab2.log .. _ab4.log, shared inputs): 512³
-# 0.365-0.368 vs 0.373-0.389 ms; at 768 (6 compute waves, one workgroup per CU) it won on one box (1.189 vs 1.219)
-# and lost on another (1.283-1.318 vs 1.261): zsum there. Box stencils in fp32 stay on zsum unless BAND=R asks.
-BAND_F32_STAR_MAX_X = 512
-BAND_ZC_STAR_F32 = 16
-BAND_TRIM = BAND_TRIM_DEFAULT
-# zero-padded image rows (x neighbours read from LDS, no DPP / boundary selects) for box stencils
-# (profiles/r04_op_band_ab6.log): 27-point 768³ 0.699 vs 0.715 ms, 1024³ 1.581 vs 1.603, 512³ 0.198 vs 0.201;
-# fp16 7-point 768³ 0.631 vs 0.629, 1024³ 1.444 vs 1.438 (not for star stencils)
-BAND_PAD_BOX = 1
-# partial rows on a padded image filled through registers (BREG) for star stencils on fp16 rows of odd length
-# (profiles/r04_op_band_ab9.log): 7-point 511³ 0.210 vs 0.217 ms (DMA row pieces + v_perm realignment); even rows
-# (510³ 0.207 vs 0.201) and box stencils (27-point 510³ 0.259 vs 0.245, 511³ 0.259 vs 0.252) keep the DMA pieces
-BAND_REG_STAR_ODD = 1
-# fp32 star stencils on rows with no whole-wave band height (idle lanes, hip_band.band_choice): the band up to this
-# row length (7-point 512²×520 0.389 vs 0.632 ms on zsum, profiles/r04_op_band_idle.log)
-BAND_F32_IDLE_MAX_X = 1024
-
-# (CX, NR) candidates of the LDS-DMA plane ring for stencils that are not linear off the centre plane
-# (hip_emitter._ring_ws_geometry), widest first: the first whose ring fits the LDS
-RING_WS_TILES = ((4, 4), (4, 2), (2, 4), (2, 2), (1, 4), (1, 2), (1, 1))
-
-# gpu_indexing_params keys of pystencils' own GPU indexing (``block_size``, ``maximum_block_size``, …, e.g.
-# ``gpu_indexing_params={'block_size': (8, 4, 2)}`` in the reference's tests/test_graph_datahandling.py:70): they
-# describe a one-thread-per-cell launch these schedules do not have, so they are accepted and ignored. Upper-case
-# keys are this layer's tile parameters; an unknown one is a typo and raises.
-TILE_KEYS = ('CX', 'WX', 'NR', 'ZMIN', 'ZMAX', 'BLK', 'D', 'NW', 'NT_STORE', 'ZSUM', 'PK', 'WS', 'AR', 'VIEW2D', 'ZC',
-             'BLOCKS', 'MAP', 'BAND', 'BTY', 'BTRIM', 'BEDGE', 'BPAD', 'BZF', 'BREG', 'BNT', 'BFREE', 'BTAIL',
-             'SFAST', 'SLP', 'PR', 'PD')
-# Ablation knobs that make results WRONG (timing probes: ``BABL``). They are not tile keys — ``gpu_indexing_params`` and
-# ``PSAD_MARCH`` reject them — and reach the planner only through this dict, which nothing on the op's path writes:
-# a probe script sets it explicitly (``scripts/probes/op_band_ab.py``) and clears it again.
-PROBE_KEYS = ('BABL',)
-PROBE_KNOBS = {}
-
-
-def _band_config(ir, ve, shape, over):
-    """The row-band schedule (``hip_band``) for the stencils it fits — fp16 storage, and fp32 star stencils on rows of
-    up to ``BAND_F32_STAR_MAX_X`` / ``BAND_F32_IDLE_MAX_X`` elements — when the row length is known and no tile
-    override asks for another schedule (``BAND=0`` or ``PSAD_BAND=0`` turn it off, ``BAND=R`` / ``BTY`` pick
-    rows per lane / band height)."""
-    if shape is None or ir.ndim != 3 or os.environ.get('PSAD_BAND', '1') == '0':
-        return None
-    if 'BAND' in over:
-        if not int(over['BAND']):
-            return None
-    elif any(k in over for k in ('CX', 'WX', 'NR', 'NW', 'ZSUM', 'PK', 'WS', 'AR', 'VIEW2D')):
-        return None
-    plans = band_plans(ir)
-    X = int(shape[-1])
-    es = band_esize(ir) if plans else 0
-    ntaps = max(len(pl['w']) for pl in plans) if plans else 0
-    whole = band_choice(X, len(plans), es, star=ntaps <= 12) if plans else None
-    if whole is not None and whole[:2] == (16, 2) and 'BAND' not in over:
-        # the wide-row 16-row band (one workgroup per CU) only where its launch still fills three rounds of the
-        # chip with the chunk length it would take (a 96×768² slab would get 576 workgroups: 8-row bands there)
-        nty16, Z = -(-int(shape[-2]) // 16), int(shape[0])
-        zc16 = BAND_ZC_STAR if ntaps <= 12 else next((c for c in BAND_ZC_BOX_LADDER if nty16 * -(-Z // c) >=
-                                                      BAND_ROUND_WG), BAND_ZC_BOX_LADDER[-1])
-        if nty16 * -(-Z // zc16) < BAND_ROUND_WG:
-            whole = band_choice(X, len(plans), es, star=ntaps <= 12, wide16=False)
-    if plans and es == 4 and 'BAND' not in over and \
-            not (ntaps <= 12 and X <= (BAND_F32_STAR_MAX_X if whole else BAND_F32_IDLE_MAX_X)):
-        return None
-    # rows with no band height of whole compute waves: a band whose last compute wave holds idle lanes
-    choice = whole or (band_choice(X, len(plans), es, idle=True) if plans else None)
-    if choice is None:
-        return None
-    TY, R, D = choice
-    pad = int(over.get('BPAD', BAND_PAD_BOX if ntaps > 12 else 0))
-    reg = int(over.get('BREG', BAND_REG_STAR_ODD if ntaps <= 12 and es == 2 and X % 2 and not int(over.get('BFREE', 0))
-                       else 0))                 # (the LDS handshake takes the LDS-DMA loader)
-    # fp32 star stencils: 8-row bands of 4 rows per lane (see BAND_F32_STAR_MAX_X) — one output only (band_choice's
-    # rule: at most 2 rows per lane when a kernel stores two fields)
-    g8 = band_geometry(X, 8, 4, 2, 4, pad, reg) if es == 4 and len(plans) == 1 else None
-    if g8 and ntaps <= 12 and 'BAND' not in over and g8['ntask'] % 64 == 0 and g8['NCT'] <= 960 and \
-            2 * g8['NI'] <= 63 and g8['lds_bytes'] <= 160 * 1024:
-        TY, R, D = 8, 4, 2
-    zc0 = int(over.get('ZMIN', BAND_ZC_BOX if ntaps > 12 else BAND_ZC_STAR))
-    if ntaps > 12 and es == 2 and (X // 8) % 128 == 0 and R == 4 and \
-            -(-int(shape[-2]) // 16) * -(-int(shape[0]) // zc0) >= BAND_MIN_WG:
-        # box stencils on rows of a multiple of 1024 halves: 16-row bands, one plane in flight (18/16 rows read per
-        # band instead of 10/8; 72 KB LDS): 27-point 1024³ fwd+bwd 1.712-1.719 vs 1.764-1.766 ms with 8-row bands
-        # (profiles/r03_op_band_ab5.log, _ab6.log); the 7-point star stencil loses (1.65 vs 1.42), 768-wide rows too
-        TY, D = 16, 1
-        rule16 = True
-    else:
-        rule16 = False
-    if 'BAND' in over:
-        R = int(over['BAND'])
-    TY = int(over.get('BTY', TY if TY % R == 0 else R * max(1, TY // R)))
-    D = int(over.get('D', D))
-    g = band_geometry(X, TY, R, D, es, pad, reg, free=int(over.get('BFREE', 0)))
-    if TY % R or g['NCT'] > 960 or D * g['NI'] > 63 or g['lds_bytes'] > 160 * 1024 or g['NT'] > 1024:
-        raise ValueError(f'band schedule: BTY={TY} BAND={R} D={D} do not fit rows of {X} elements')
-    nty, Z = -(-int(shape[-2]) // TY), int(shape[0])
-    min_wg = BAND_MIN_WG
-    if ntaps <= 12 and es == 4:
-        zc = BAND_ZC_STAR_F32
-    elif ntaps <= 12:
-        long_ok = X <= BAND_STAR_LONG_MAX_X and nty * -(-Z // BAND_ZC_STAR_LONG) >= BAND_STAR_LONG_MIN_WG
-        zc = BAND_ZC_STAR_LONG if long_ok else BAND_ZC_STAR
-        min_wg = BAND_STAR_LONG_MIN_WG if long_ok else BAND_MIN_WG
-    elif TY == 16 and rule16:
-        zc = BAND_ZC_BOX16              # (16-row bands of other rows — 2 rows per lane, idle lanes — take the ladder)
-    else:
-        zc = next((c for c in BAND_ZC_BOX_LADDER if nty * -(-Z // c) >= BAND_ROUND_WG), BAND_ZC_BOX_LADDER[-1])
-    zc = int(over.get('ZMIN', zc))
-    if 'BAND' not in over and nty * -(-Z // zc) < min_wg:
-        return None
-    zmax = int(over.get('ZMAX', zc))
-    btrim = int(over.get('BTRIM', BAND_TRIM))
-    if btrim == 3 and (zmax != zc or zc < 3):
-        if 'BTRIM' in over:
-            raise ValueError('band schedule: BTRIM=3 needs ZMIN == ZMAX >= 3')
-        btrim = 1                       # chunk length not fixed at compile time: peel the chunk's first planes only
-    return MarchConfig(VE=ve, BAND=R, BTY=TY, BX=X, D=D, ZSUM=True, NT_STORE=True, ZMIN=zc,
-                       ZMAX=zmax, BLK=int(over.get('BLK', 512)), MAP=int(over.get('MAP', 0)),
-                       BTRIM=btrim, BEDGE=int(over.get('BEDGE', 1)), BPAD=pad, BZF=int(over.get('BZF', 1)), BREG=reg,
-                       BNT=int(over.get('BNT', 2)), BFREE=int(over.get('BFREE', 0)), BTAIL=int(over.get('BTAIL', 1)),
-                       BABL=int(PROBE_KNOBS.get('BABL', 0)))
-
-
-def ws_fallback_config(cfg):
-    """The register-prefetch form of a WS (LDS-DMA loader) config, for planes beyond the loader's 32-bit buffer
-    offsets: eight compute waves exist only on the LDS-DMA ring, so NW drops to 4 (and WX to at most 4) as in
-    ``default_march_config``'s own fallback."""
-    c = {**cfg.__dict__, 'WS': False}
-    if c['NW'] == 8:
-        c['NW'], c['WX'] = 4, min(c['WX'], 4)
-    return MarchConfig(**c)
-
-
-def default_march_config(ir, ve, shape=None, tuning=None, band=True):
-    """Tile shape for a kernel and field shape (measured on MI355X).
-
-    3-D stencils linear in their off-centre planes use the z-partial-sum schedule (``emit_zsum``):
-    star stencils (7-point) with a 256×32 tile (CX=4, NR=8), box stencils (27-point) with a
-    128×16 tile and 32-plane chunks; fp64 halves the tile width (register pressure). Other 3-D
-    stencils use the LDS ring ("lite" ring when planes behind the centre are read only at (0,0)).
-    2-D fields run as (1, Y, X) tiles of 256×16. Non-temporal stores for 3-D outputs (written
-    once, never re-read by the sweep). Overrides: ``gpu_indexing_params`` or
-    ``PSAD_MARCH="CX=..,NR=.."``.
-    """
-    from .hip_emitter import lite_fields
-    star_ws = False
-    cfg = dict(CX=4, WX=1, NR=8, NT_STORE=True, VIEW2D='yx', ZSUM=False, PK=False,
-               ZMIN=32, ZMAX=64, BLK=512)
-    probe = MarchConfig(VE=ve, **cfg)
-    zsum_ok = zsum_plan(ir, probe) is not None
-    if ir.ndim == 3 and set(ir.stencil_fields) - lite_fields(ir, probe):
-        if zsum_ok:      # box stencil linear off-centre (27-point): z partial sums, small tile, short chunks
-            # 768³ fp16: 0.460 ms (packed fp32 FMAs over column pairs, 2 waves side by side in x)
-            # vs 0.469 scalar WX=1 vs 0.70 ms LDS ring; unrolling the plane loop 3x is slower (0.53-0.56)
-            # chunks of 16..32 planes, ~2048 workgroups: 768³ 32 planes; one 8-GPU slab (96×768²) 16
-            # planes, 0.067 vs 0.073 ms at 32
-            # tap pairs by inline-asm ds_read2_b32 (AR): 0.421 vs 0.459 ms at 768³, 0.062 vs 0.067 ms per
-            # 8-GPU slab (profiles/r01_tune_27pt_ar.log) — the compiler's adjacent-x merges cost 26 v_mov
-            cfg.update(CX=2, WX=2, NR=4, ZSUM=True, PK=True, AR=True, ZMIN=16, ZMAX=32, BLK=2048)
-            half = dict(CX=4, WX=1, NR=2, WS=True, D=3, ZMIN=24, ZMAX=24)
-            if ws_geometry(ir, MarchConfig(VE=ve, **{**cfg, **half})):
-                # fp16 storage: LDS-DMA loader wave into a half-precision ring, lanes own x-adjacent quads,
-                # taps converted in registers (emit_zsum -> _emit_zsum_half), 256×8 tiles, 24-plane chunks:
-                # 768³ 0.370-0.392 ms vs 0.431-0.448 ms for the register-prefetch AR form in the same
-                # process; 96×768² slab 0.048-0.055 vs 0.059-0.069 ms (profiles/r02_tune_27pt_half*.log)
-                cfg.update(half)
-        else:
-            cfg.update(CX=2, NR=4)                             # box stencil: full ring, LDS/VALU bound
-    elif ir.ndim == 3 and zsum_ok:
-        cfg.update(ZSUM=True)                                  # 1024³ 7-point: 1.495 ms vs 1.629 ms lite ring
-        ws0 = ws_geometry(ir, MarchConfig(VE=ve, **{**cfg, 'WS': True}))
-        if ws0:
-            # star stencils, storage = compute type: LDS-DMA loader wave, 4 planes in flight, 256×16 tiles,
-            # 128-plane chunks (one 5-wave workgroup per CU). 1024³ 7-point 1.411 ms vs 1.506 ms register
-            # prefetch (128×32 tiles); one 8-GPU slab 0.182 vs 0.187 ms (profiles/r01_tune_ws_*.log).
-            # fp16 storage (half-precision ring): 256×32 tiles, the same 16 KB per plane and workgroup:
-            # 7-point fp16 1024³ 0.786 vs 0.889 ms, 768³ 0.372 vs 0.405, 128×1024² slab 0.092 vs 0.098,
-            # 512³ 0.086 vs 0.087 (profiles/r02_tune_f16s_*.log). Chunks down to 8 planes: small domains are
-            # latency bound with few long chunks (128³ 0.0106 vs 0.0197-0.021 ms, 256³ 0.0244 vs 0.032-0.036;
-            # the chunk model keeps 1024³ / 768³ / 512³ / the 8-GPU slabs where they were,
-            # profiles/r02_tune_small_*.log)
-            cfg.update(WS=True, CX=4, NR=8 if ws0['kind'] == 'h' else 4, D=4, ZMIN=8, ZMAX=128, BLK=256)
-            star_ws = True
-    ring_ws = False                       # (the LDS-DMA plane ring of nonlinear stencils, 3-D or 2-D along axis 0)
-    if ir.ndim == 3 and not zsum_ok:
-        # stencils not linear off the centre plane (products / functions of neighbour taps): the plane ring fed by
-        # an LDS-DMA loader wave, 2 planes in flight, the widest tile whose ring fits the LDS
-        tiles = RING_WS_TILES
-        if pair_ok(ir) and any(storage_ctype(f) == '_Float16' for f in ir.stencil_fields):
-            # fp16 planes in the ring, taps as whole dwords of cell pairs (PR): 128×8 tiles, two planes in flight, for
-            # two ring fields (varcoef forward), 128×4 and three in flight for more (its adjoint: three fields). 768³
-            # fwd / bwd 0.618–0.634 / 1.066–1.095 ms vs 0.67–0.69 / 1.16–1.17 on the register ring
-            # (profiles/r06_hring_f16.log, r06_hring_f16b.log: 20 tilings, 8 compute waves and deeper rings slower)
-            two = len(ir.stencil_fields) <= 2
-            tiles = [(2, 2 if two else 1)]
-            cfg['PR'] = 1
-        half_vec = ir.has_index_dims and any(storage_ctype(f) == '_Float16' for f in ir.stencil_fields)
-        if half_vec:
-            # vector fields in fp16 (fp16 images, taps converted): 128×8 tiles. Lanes own x-adjacent cell pairs with
-            # packed fp32 statements (PR) where the statements allow — a lane's elements are then contiguous from an
-            # even offset and its reads merge; eight compute waves for the adjoint's two ring fields. Advection u(3)
-            # 256³ fwd / bwd 0.052 / 0.054 ms vs 0.063 / 0.063 per cell, 0.139 / 0.069 on the widest fitting tile
-            # (256×16), 0.131 / 0.153 one thread per cell (profiles/r06_vec16_tiles.log, r06_vec16_pairs.log; fp32
-            # vector fields measured slower as pairs: 0.075 / 0.12 vs 0.071 / 0.095)
-            tiles = [(2, 2)]
-            if pair_ok(ir, vectors=True):
-                cfg['PR'] = 1
-        for cx, nr in tiles:
-            c = {**cfg, 'CX': cx, 'NR': nr, 'WS': True, 'D': 2 if nr == 2 or not cfg.get('PR') else 3, 'ZMIN': 8,
-                 'ZMAX': 128, 'BLK': 256}
-            if half_vec and len(ir.stencil_fields) > 1:
-                c['NW'] = 8
-            w = ws_geometry(ir, MarchConfig(VE=ve, **c))
-            if w is not None and w['lds_bytes'] <= 160 * 1024:
-                cfg.update(c)
-                ring_ws = True
-                break
-        if not ring_ws:
-            cfg['PR'] = 0                 # (the register ring stores fp32 images: pairs measured neutral there)
-    if ir.ndim == 3 and not zsum_ok and not ring_ws:
-        # nonlinear stencils on the register-prefetch ring (fp16 storage: the LDS-DMA ring holds the compute type):
-        # 128×8 tiles, four workgroups per CU — varcoef fp16 768³ fwd / bwd 0.69–0.71 / 1.16–1.18 ms vs 0.81 / 1.31–1.34
-        # with the budget's 256×16 / 256×8 (profiles/r06_varcoef_f16_tiles.log: latency, not VALU — packed cell pairs
-        # or two planes in flight on the wide tiles gave nothing, r06_varcoef_pairs_f16.log, r06_varcoef_pd2_f16.log)
-        cfg.update(CX=2, NR=2)
-    if ir.ndim == 2:
-        cfg.update(CX=4, WX=1, NR=4, VIEW2D='yx', NT_STORE=False)   # 256×16 tiles (4096²: 0.024 ms, 5.6 TB/s)
-        plans2 = zsum_plan(ir, probe)
-        if plans2 is None or any(pl['rest'] != 0 for pl in plans2):
-            # nonlinear 2-D stencils (one tile per workgroup, nothing to pipeline): 128×8 tiles, more workgroups in
-            # flight — 2-D varcoef 4096² fp32 fwd / bwd 0.52 / 0.51 of 8 TB/s vs 0.49 / 0.38 on 256×16, fp16 0.30 /
-            # 0.35 vs 0.28 / 0.21 (profiles/r06_nl2d.log)
-            cfg.update(CX=2, NR=2)
-            # ... and on long 16-byte-piece rows: march along axis 0 (VIEW2D='zy', rows as the planes of the LDS-DMA
-            # ring, four waves side by side in x: 512-cell row strips; fp16 as x-adjacent cell pairs), 512 / 1024
-            # workgroups of 64 / 32 rows at 4096²: 2-D varcoef 4096² fp32 fwd / bwd 0.61 / 0.57–0.58 of 8 TB/s,
-            # fp16 0.40–0.42 / 0.49 (profiles/r06_nl2d_zy.log: 40 tilings and chunkings; the register ring along
-            # axis 0 was slower, 0.41 / 0.41, and 128-row chunks 0.51 / 0.49)
-            # (fp64: 1024-cell strips, not halved below — fwd / bwd 0.56–0.62 / 0.58–0.61 vs 0.55–0.56 / 0.53–0.56 on
-            # the (1, Y, X) tiles; 256-cell strips lost the adjoint, 0.53, profiles/r06_nl2d_f64.log)
-            half2 = any(storage_ctype(f) == '_Float16' for f in ir.stencil_fields)
-            wide = np.dtype(ir.compute_dtype).itemsize == 8
-            zy = dict(VIEW2D='zy', NR=1, NW=4, WX=4, CX=4 if wide else 2, WS=True, D=2, ZMIN=16 if half2 else 32,
-                      ZMAX=64, BLK=1024 if half2 else 512, PR=1 if half2 and pair_ok(ir, vectors=True) else 0)
-            if ir.stencil_fields and (shape is None or int(shape[-1]) >= 64 * zy['CX'] * zy['WX']):
-                w = ws_geometry(ir, MarchConfig(VE=ve, **{**cfg, **zy}))
-                if w is not None and w['lds_bytes'] <= 160 * 1024:
-                    cfg.update(zy)
-                    ring_ws = True
-    if ir.has_index_dims and not ring_ws:
-        # vector fields (components interleaved in the plane image) linear off the centre plane: the zsum schedule;
-        # narrower tiles keep the image (TX + 2H)·C elements wide (the plane ring picked its tile above)
-        from .hip_emitter import ncomp
-        cmax = max([ncomp(f) for f in ir.stencil_fields] + [1])
-        cfg.update(ZSUM=True, PK=False, AR=False)
-        while cfg['CX'] > 1 and cfg['CX'] * cmax > 4:
-            cfg['CX'] //= 2
-    if np.dtype(ir.compute_dtype).itemsize == 8 and not (ir.ndim == 2 and ring_ws):
-        cfg['CX'] = max(1, cfg['CX'] // 2)                     # fp64: half-width tiles (512³: 0.380 vs 0.536 ms)
-    elif ir.ndim == 3 and cfg['ZSUM'] and not cfg['PK'] and not cfg.get('WS'):
-        # star stencils: 128×32 tiles, two workgroups per CU. 512³ / one 8-GPU slab of 1024³
-        # (128×1024²): 0.191 / 0.187 ms vs 0.214 / 0.208 ms with 256×32 tiles; 1024³ a tie
-        cfg['CX'] = 2
-    env = os.environ.get('PSAD_MARCH')
-    over = {k: v for k, v in dict(tuning or {}).items() if not k.islower()}     # pystencils indexing keys: ignored
-    if env:
-        for kv in env.split(','):
-            k, v = kv.split('=')
-            over[k.strip()] = v.strip() if k.strip() == 'VIEW2D' else int(v)
-    view_yx = ir.ndim == 2 and str(over.get('VIEW2D', cfg['VIEW2D'])) != cfg['VIEW2D']
-    if ring_ws and (any(k in over for k in ('CX', 'WX', 'NR', 'NW')) or view_yx) and 'WS' not in over:
-        cfg.update(WS=False, D=3)           # a tile override on the ring: the register-prefetch form it was sized for
-        if ir.ndim == 2:
-            cfg.update(VIEW2D='yx', NW=4, WX=1, NR=2, PR=0, ZMIN=32, ZMAX=64, BLK=512,   # (the 2-D one: (1, Y, X) tiles)
-                       CX=1 if np.dtype(ir.compute_dtype).itemsize == 8 else 2)
-            if ir.has_index_dims:
-                cfg.update(ZSUM=True, PK=False, AR=False)     # (vector fields: the zsum plane, as without the ring)
-            ring_ws = False
-    for k, v in over.items():
-        if k not in TILE_KEYS:
-            raise ValueError(f"unknown tile parameter '{k}' (gpu_indexing_params / PSAD_MARCH)")
-        if k in ('CX', 'WX', 'NR', 'ZMIN', 'ZMAX', 'BLK', 'D', 'NW', 'MAP'):
-            cfg[k] = int(v)
-        elif k in ('NT_STORE', 'ZSUM', 'PK', 'WS', 'AR'):
-            cfg[k] = bool(int(v)) if not isinstance(v, bool) else v
-        elif k == 'VIEW2D':
-            cfg[k] = str(v)
-        elif k in ('SFAST', 'SLP', 'PR', 'PD'):
-            cfg[k] = int(v)
-    if cfg.get('PR') and 'PR' not in over and (cfg['CX'] % 2 or not pair_ok(ir, vectors=bool(cfg.get('WS')))):
-        cfg['PR'] = 0          # a tile override the default pair form cannot take (odd CX; vector fields off the ring)
-    if ring_ws and PROBE_KNOBS.get('BABL'):
-        cfg['BABL'] = int(PROBE_KNOBS['BABL'])   # (timing probe of the march ring, as on the band: 3 = no plane loads)
-    bc = _band_config(ir, ve, shape, over) if band else None
-    if bc is not None:
-        return bc
-    if 'NW' in over and 'WX' not in over:
-        cfg['WX'] = min(cfg['WX'], cfg['NW'])
-    if cfg['ZSUM'] and zsum_plan(ir, MarchConfig(VE=ve, **cfg)) is None:
-        cfg['ZSUM'] = False                                    # not eligible: LDS ring instead
-    cmin = 2 if cfg.get('PR') and not cfg['ZSUM'] else 1      # packed cell pairs: two cells per lane and column
-    if shape is not None:
-        X = int(shape[-1])
-        if 'CX' not in over:
-            while cfg['CX'] > cmin and 64 * cfg['CX'] * cfg['WX'] // 2 >= X:
-                cfg['CX'] //= 2
-            tx = 64 * cfg['CX'] * cfg['WX']
-            ws0 = ws_geometry(ir, MarchConfig(VE=ve, **cfg)) if cfg.get('WS') else None
-            quads = ws0 is not None and ws0['kind'] == 'h'       # the half ring needs lanes owning quads
-            if cfg.get('WS') and cfg['CX'] > cmin and -(-X // (tx // 2)) * (tx // 2) < -(-X // tx) * tx and \
-                    (not quads or (cfg['CX'] // 2) % 4 == 0):
-                # WS tiles: half width when it pads x less (384³ 7-point: 0.116 → 0.081 ms with 48-plane
-                # chunks, profiles/r01_tune_odd_sizes.log)
-                cfg['CX'] //= 2
-        if 'WX' not in over:
-            while cfg['WX'] > 1 and 64 * cfg['CX'] * cfg['WX'] // 2 >= X:
-                cfg['WX'] //= 2
-        ny = int(shape[-2]) if ir.ndim == 3 or cfg['VIEW2D'] == 'yx' else 1
-        if 'NR' not in over:
-            while cfg['NR'] > 1 and (cfg.get('NW', 4) // cfg['WX']) * cfg['NR'] // 2 >= ny:
-                cfg['NR'] //= 2
-    # LDS budget: two workgroups per CU (≤ 80 KB) for the register-prefetch defaults, the 160 KB hardware
-    # limit for the LDS-DMA ring and for explicit tile overrides
-    budget = 80 * 1024 if not ('CX' in over or 'NR' in over or cfg.get('WS')) else 160 * 1024
-
-    def lds(c):
-        mc = MarchConfig(VE=ve, **c)
-        ws = ws_geometry(ir, mc)
-        return ws['lds_bytes'] if ws else march_geometry(ir, mc)['lds_bytes']
-    while cfg.get('WS') and cfg.get('D', 3) > 1 and lds(cfg) > 160 * 1024:
-        cfg['D'] = cfg.get('D', 3) - 1                          # fewer planes in flight before smaller tiles
-    while lds(cfg) > budget and (cfg['NR'] > 1 or cfg['CX'] > cmin):
-        if (cfg['NR'] >= cfg['CX'] or cfg['CX'] <= cmin) and cfg['NR'] > 1:
-            cfg['NR'] //= 2
-        else:
-            cfg['CX'] //= 2
-    if cfg.get('WS') and not cfg['ZSUM'] and lds(cfg) > 160 * 1024:
-        # a plane ring that does not fit even at the smallest tile (many fields of wide radius): the register form
-        cfg['WS'] = False
-        if cfg.get('NW', 4) == 8:                             # (eight compute waves only on the LDS-DMA ring)
-            cfg['NW'], cfg['WX'] = 4, min(cfg['WX'], 4)
-        while lds(cfg) > budget and (cfg['NR'] > 1 or cfg['CX'] > cmin):
-            if (cfg['NR'] >= cfg['CX'] or cfg['CX'] <= cmin) and cfg['NR'] > 1:
-                cfg['NR'] //= 2
-            else:
-                cfg['CX'] //= 2
-    if ir.ndim == 3 and lds(cfg) > 160 * 1024:
-        raise ValueError(f'no tile of this kernel fits the 160 KB LDS ({lds(cfg)} B at {cfg})')
-    if star_ws and cfg.get('WS') and shape is not None and 'MAP' not in over:
-        ntx = -(-int(shape[-1]) // (64 * cfg['CX'] * cfg['WX']))
-        if ntx & (ntx - 1):
-            # tiles per row not a power of two: dispatch order instead of the XCD-aware remap. Through the op,
-            # fwd + bwd, same process (scripts/probes/map_ab.py, profiles/r03_map_ab.log): 768³ fp32 -8.6 %
-            # (5.91 / 5.78 TB/s), 640³ -4.4 %, 768³ fp16 -4.7 %, 640³ fp64 -2.5 %; with 2 or 4 tiles per row
-            # the dispatch order pins each XCD to the same x columns of every plane: 1024³ +10 %, 128×1024²
-            # +10 %, 512³ fp64 +6 % — those keep the remap
-            cfg['MAP'] = 1
-    return MarchConfig(VE=ve, **cfg)
 
 
 def _torch():
@@ -757,53 +375,19 @@ class HipStencilKernel:
         """(Z, Y, X), bounds and grid of the march schedule for a field shape; ``slots`` = resident
         workgroups (``_resident_slots``) switches the WS schedule to quantisation-aware chunks."""
         ir = self.ir
-        bounds = ir.iteration_bounds(shape)
-        if z_limits is not None:
-            bounds[0] = (int(z_limits[0]), int(z_limits[1]))
-        if z_range is not None and _is_pair(z_range):
-            (a0, a1), (b0, b1) = [(int(a), int(b)) for a, b in z_range]
-            lo, hi = bounds[0]
-            if ir.ndim == 2 and cfg.VIEW2D == 'yx':
-                raise ValueError("z ranges need the 'zy' view of 2-D fields")
-            if not (lo <= a0 < a1 <= b0 < b1 <= hi) or a1 - a0 != b1 - b0:
-                raise ValueError(f'z_range pair {z_range} must be disjoint, ordered, of equal length '
-                                 f'and inside [{lo}, {hi})')
-            geo = self.march_launch_geometry(shape, cfg, (a0, b1), z_limits=z_limits)
-            zc = a1 - a0
-            geo.update(zlo=a0, zhi=b1, zc=zc, zstep=b0 - a0, grid=geo['ntx'] * geo['nty'] * 2)
-            return geo
-        if z_range is not None:
-            lo, hi = bounds[0]
-            bounds = [(max(lo, int(z_range[0])), min(hi, int(z_range[1])))] + list(bounds[1:])
-        if ir.ndim == 3:
-            Z, Y, X = shape
-            (zlo, zhi), (ylo, yhi), (xlo, xhi) = bounds
-        elif cfg.VIEW2D == 'yx':
-            Z, (Y, X) = 1, shape
-            (zlo, zhi) = (0, 1)
-            (ylo, yhi), (xlo, xhi) = bounds
-            if z_range is not None:
-                raise ValueError("z ranges need the 'zy' view of 2-D fields")
-        else:
-            Z, X = shape
-            Y = 1
-            (zlo, zhi), (xlo, xhi) = bounds
-            ylo, yhi = 0, 1
-        if cfg.BAND:            # full-row bands (hip_band): one band column, x handled inside the kernel
-            ntx, nty = 1, max(1, math.ceil(yhi / cfg.BTY))
-        else:
-            ntx = max(1, math.ceil((X if cfg.XB else xhi) / cfg.TX))
-            nty = max(1, math.ceil(yhi / cfg.TY))
-        nt = ntx * nty
-        nz = max(0, zhi - zlo)
+        geo = march_extents(ir, shape, cfg, z_range, z_limits)
+        nt, nz = geo['ntx'] * geo['nty'], max(0, geo['zhi'] - geo['zlo'])
+        if z_range is not None and _is_pair(z_range):       # the two faces: one chunk each, zstep planes apart
+            (a0, a1), (b0, _) = z_range
+            return dict(geo, zc=int(a1) - int(a0), zstep=int(b0) - int(a0), grid=2 * nt)
         # chunk length: aim at ~2 workgroups per CU (512 blocks), ZMIN..ZMAX planes per chunk (each chunk
         # re-reads 2·RZ halo planes). 7-point 1024³, 128×32 tiles: 64-plane chunks 1.536 ms vs 128-plane
         # 1.570 ms (profiles/r01_tune_cx_ab_1024.log); 512³ and 128×1024² slabs land on 64 by the target
-        target = int(self.kernel.tuning.get('BLOCKS', os.environ.get('PSAD_MARCH_BLOCKS', cfg.BLK)))
-        zc = self.kernel.tuning.get('ZC') or int(os.environ.get('PSAD_MARCH_ZC', 0)) or \
+        env_zc, env_blocks = os.environ.get('PSAD_MARCH_ZC'), os.environ.get('PSAD_MARCH_BLOCKS')
+        target = int(self.kernel.tuning.get('BLOCKS', cfg.BLK if env_blocks is None else env_blocks))
+        zc = self.kernel.tuning.get('ZC') or int(0 if env_zc is None else env_zc) or \
             min(nz, max(cfg.ZMIN, min(cfg.ZMAX, math.ceil(nz * nt / target))))
-        explicit = self.kernel.tuning.get('ZC') or os.environ.get('PSAD_MARCH_ZC') or \
-            'BLOCKS' in self.kernel.tuning or os.environ.get('PSAD_MARCH_BLOCKS')
+        explicit = self.kernel.tuning.get('ZC') or env_zc or 'BLOCKS' in self.kernel.tuning or env_blocks
         cus = _torch().cuda.get_device_properties(_torch().cuda.current_device()).multi_processor_count \
             if slots else 0
         # measured on the default WS tiles (one workgroup per CU, or the half-width tiles it picks for
@@ -826,107 +410,19 @@ class HipStencilKernel:
             # equal chunks: same chunk count (same halo re-reads), no short tail chunk — 27-point fp16
             # 192×768² slab: 27 → 24 planes, 0.129 → 0.113 ms (profiles/r01_tune_zc_slab.log)
             zc = math.ceil(nz / nchunks)
-        return dict(Z=Z, Y=Y, X=X, zlo=zlo, zhi=zhi, ylo=ylo, yhi=yhi, xlo=xlo, xhi=xhi, zc=zc, zstep=zc,
-                    ntx=ntx, nty=nty, grid=nt * nchunks)
+        return dict(geo, zc=zc, zstep=zc, grid=nt * nchunks)
 
     def _plan_march(self, tensors, halo_list, shape, device, z_range, x_border=False, z_limits=None,
                     start_signal=False, halo_wait=False):
-        torch = _torch()
         ir = self.ir
-        ve = self._vec_elems()
-        X = shape[-1]
         stencil = ir.stencil_fields
         by_name = {f.name: t for f, t in zip(ir.fields, tensors)}
-        esize = 16 // ve
-
-        def fits(v, step=None):
-            step = v * esize if step is None else step
-            return (step != v * esize or X % v == 0) and \
-                all(by_name[f.name].data_ptr() % step == 0 for f in stencil) and \
-                all(h.data_ptr() % step == 0 for h in halo_list if h is not None)
-        bu = None
-        dword_rows = (X * esize) % 4 == 0 and fits(ve, step=4) and all(t.data_ptr() % 4 == 0 for t in tensors)
-        half_rows = esize == 2 and X % 2 == 1          # fp16 rows on half dwords: realigned in registers ('bo')
-        if not fits(ve) and (dword_rows or half_rows) and not ir.has_index_dims and \
-                int(np.prod(shape[1:])) * esize < 2 ** 31 - 1024 and os.environ.get('PSAD_BAND_UNALIGNED', '1') != '0':
-            # rows whose pitch is not a multiple of 16 bytes on the row-band schedule: row-wise dword-aligned pieces,
-            # a 16-byte row pitch in LDS, the partial last chunk stored as dwords (hip_band, 'bu')
-            c = self._march_cfg(ve, shape, band=True)
-            bu = c if c.BAND else None
-        xm = False
-        if bu is None and not fits(ve) and (X * esize) % 4 == 0 and fits(ve, step=4) and not ir.has_index_dims and \
-                all(np.dtype(f.dtype.numpy_dtype).itemsize == esize for f in ir.fields) and \
-                int(np.prod(shape[1:])) * esize < 2 ** 31 - 1024:       # (the loader's 32-bit offsets, below)
-            # rows whose pitch is not a multiple of 16 bytes but of 4 (fp32 / fp64, fp16 with X even): the LDS-DMA
-            # ring still takes 16-byte pieces (dword-aligned; the image in LDS keeps its layout) and zero-fills
-            # past each row end (XM) — where the WS schedule applies
-            probe = self._march_cfg(ve, shape, band=False)
-            xm = bool(probe.WS) and probe.ZSUM and ws_geometry(ir, probe) is not None
-        xo = False
-        if not xm and not fits(ve) and esize == 2 and not ir.has_index_dims and os.environ.get('PSAD_XO', '1') != '0' and \
-                all(np.dtype(f.dtype.numpy_dtype).itemsize == 2 for f in ir.fields) and \
-                int(np.prod(shape[1:])) * 2 < 2 ** 31 - 1024:
-            # fp16 rows starting on half dwords (X odd, or an odd-element base): the half-precision LDS-DMA ring
-            # loads such rows one element early and shifts them back in LDS (XO) — 255³ fp16 instead of the
-            # register-prefetch path
-            probe = self._march_cfg(ve, shape, band=False)
-            ws_p = ws_geometry(ir, probe) if probe.WS else None
-            xo = ws_p is not None and ws_p['kind'] == 'h'
-        if bu is not None:
-            cfg = bu
-        elif xm or xo:
-            cfg = MarchConfig(**{**self._march_cfg(ve, shape, band=False).__dict__, 'XM': True,
-                                 'XO': (1 if X % 2 else 2) if xo else 0})
-        else:
-            # widest plane-load vector the rows allow: 16 bytes (and the LDS-DMA loader) when the row pitch is a
-            # multiple of 16 bytes, else 8 / 4 bytes (register-prefetch loads) before scalar ones — X = 262
-            # fp32: 8-byte loads instead of 4-byte (profiles/r02_misaligned*.log)
-            ve = next(v for v in (ve, ve // 2, ve // 4, 1) if v >= 1 and fits(v))
-            if ve == 1 and ir.ndim == 2 and not halo_list and z_range is None and z_limits is None and \
-                    not ir.has_index_dims:
-                # 2-D rows of scalar loads: the one-thread-per-cell schedule streams them faster (4097² 5-point
-                # 0.028 vs 0.046 ms, 4095×4094 0.027 vs 0.043; profiles/r02_misaligned.log)
-                return self._plan_generic(tensors, shape, device)
-            # the row-band schedule (hip_band): 16-byte pieces and stores on every field and halo, 32-bit plane offsets
-            band_ok = ve == self._vec_elems() and all(t.data_ptr() % 16 == 0 for t in tensors) and \
-                int(np.prod(shape[1:])) * esize < 2 ** 31 - 1024
-            cfg = self._march_cfg(ve, shape, band=band_ok)
-        if halo_list and ir.ndim == 2 and cfg.VIEW2D == 'yx':
-            cfg = MarchConfig(**{**cfg.__dict__, 'VIEW2D': 'zy'})
-        from .hip_emitter import ncomp
-        if ir.has_index_dims and not cfg.ZSUM and not (cfg.WS and ws_geometry(ir, cfg)):
-            if halo_list or z_range is not None or z_limits is not None:
-                raise ValueError('vector-field kernels take halo planes / z ranges only in the zsum schedule')
+        read = [by_name[f.name] for f in stencil] + [h for h in halo_list if h is not None]
+        cfg = resolve_march(ir, self.kernel.tuning, shape, min([_align_class(t.data_ptr()) for t in read] + [5]),
+                            min(_align_class(t.data_ptr()) for t in tensors), bool(halo_list), z_range, z_limits,
+                            x_border, start_signal, halo_wait)
+        if cfg is None:
             return self._plan_generic(tensors, shape, device)
-        cmax = max([ncomp(f) for f in stencil] + [1])
-        ws = ws_geometry(ir, cfg)
-        if ws and int(np.prod(shape[1:])) * cmax * max(ws['esize'], ws.get('ssize', 0)) >= 2 ** 31 - 1024:
-            # planes beyond the loader's 32-bit buffer offsets: register-prefetch form of the same schedule
-            # (never with XM: its rows straddle, which only the loader's zero fill repairs)
-            assert not cfg.XM
-            if ir.has_index_dims and not cfg.ZSUM:
-                # (the register-prefetch ring takes scalar fields only)
-                if halo_list or z_range is not None or z_limits is not None:
-                    raise ValueError('vector-field kernels beyond 32-bit plane offsets take no halo planes / z ranges')
-                return self._plan_generic(tensors, shape, device)
-            cfg = ws_fallback_config(cfg)
-        xlo, xhi = ir.iteration_bounds(shape)[-1]
-        if x_border and cfg.ZSUM and (xlo > 0 or xhi < shape[-1]) and \
-                not (ir.ndim == 2 and cfg.VIEW2D == 'zy'):
-            cfg = MarchConfig(**{**cfg.__dict__, 'XB': True})
-        if cfg.BAND:
-            # unmasked stores when every band row lies in [ylo, yhi) and the x range is whole rows
-            g0 = self.march_launch_geometry(shape, cfg, z_range, z_limits=z_limits)
-            if not (g0['ylo'] == 0 and g0['yhi'] == g0['nty'] * cfg.BTY and g0['xlo'] == 0 and g0['xhi'] == g0['X']) or \
-                    g0['X'] % (16 // esize):                          # a partial last chunk per row
-                cfg = MarchConfig(**{**cfg.__dict__, 'BMASK': True,
-                                     'BXW': g0['xlo'] == 0 and g0['xhi'] == g0['X'] and not cfg.XB})
-        if start_signal:
-            cfg = MarchConfig(**{**cfg.__dict__, 'SIG': True})
-        if halo_wait:
-            if not ((cfg.BAND and not (cfg.BREG and shape[-1] % (16 // esize))) or ws_geometry(ir, cfg)):
-                raise ValueError('a halo wait needs an LDS-DMA loader (band or WS schedule)')
-            cfg = MarchConfig(**{**cfg.__dict__, 'HWAIT': True})
         variant = ('march', cfg)
         fn = self.function(variant, device)
         ws = ws_geometry(ir, cfg)
@@ -934,28 +430,23 @@ class HipStencilKernel:
         geo = self.march_launch_geometry(shape, cfg, z_range, slots=slots, z_limits=z_limits)
         grid = geo['grid'] if geo['yhi'] > geo['ylo'] and geo['xhi'] > geo['xlo'] else 0
         rz = march_geometry(ir, cfg)['RZ']
-        plane = geo['Y'] * geo['X']
         for i, f in enumerate(stencil):
             for h in (halo_list[2 * i:2 * i + 2] if halo_list else ()):
-                if h is not None and (not isinstance(h, torch.Tensor) or not h.is_contiguous() or
-                                      h.numel() < rz * plane * ncomp(f) or h.dtype != by_name[f.name].dtype or
-                                      h.device != by_name[f.name].device):
+                if h is not None and (not isinstance(h, _torch().Tensor) or not h.is_contiguous() or
+                                      h.numel() < rz * geo['Y'] * geo['X'] * ncomp(f) or
+                                      h.dtype != by_name[f.name].dtype or h.device != by_name[f.name].device):
                     raise ValueError(f"halo for '{f.name}' must be a contiguous tensor of >= {rz} planes "
                                      "on the field's device")
         if max(geo['Z'], geo['Y'], geo['X']) >= 2 ** 31 or grid >= 2 ** 31:
             raise ValueError('field extent too large for the march schedule')
-        statics = [int(geo[k]) for k in ('Z', 'Y', 'X', 'zlo', 'zhi', 'ylo', 'yhi', 'xlo', 'xhi', 'zc', 'zstep', 'ntx',
-                                          'nty')]
+        statics = [int(geo[k]) for k in 'Z Y X zlo zhi ylo yhi xlo xhi zc zstep ntx nty'.split()]
         kinds = ['ptr'] * (len(tensors) + 2 * len(stencil)) + ['i32'] * len(statics)
-        if cfg.SIG:
-            kinds += ['ptr', 'u32']                     # the start signal: word and value, patched by the caller
-            statics += [0, 0]
-        if cfg.HWAIT:
-            kinds += ['ptr', 'u32']                     # the halo wait: word and value, patched by the caller
+        for _ in range(cfg.SIG + cfg.HWAIT):    # the start signal, the halo wait: word and value, patched by the caller
+            kinds += ['ptr', 'u32']
             statics += [0, 0]
         kinds += [self._scalar_kind()] * len(ir.scalars)
-        block = ws['block'] if ws else (band_geometry(cfg.BX, cfg.BTY, cfg.BAND, cfg.D, esize, cfg.BPAD, cfg.BREG, cfg.BFREE)['NT'] if cfg.BAND else
-                                        cfg.NT)
+        block = ws['block'] if ws else cfg.NT if not cfg.BAND else \
+            band_geometry(cfg.BX, cfg.BTY, cfg.BAND, cfg.D, 16 // cfg.VE, cfg.BPAD, cfg.BREG, cfg.BFREE)['NT']
         plan = _Plan(variant, fn, grid, kinds, len(tensors), 2 * len(stencil), statics, xb=cfg.XB, block=block)
         i = len(tensors) + 2 * len(stencil) + 13
         if cfg.SIG:
@@ -1005,15 +496,6 @@ class _Plane:
                 return False
             expect *= n
         return True
-
-
-def _align_class(p):
-    """log2 of the largest power of two (≤ 32) dividing the address ``p`` (0 counts as 32-byte aligned)."""
-    return min((p & -p).bit_length() - 1, 5) if p else 5
-
-
-def _is_pair(z_range):
-    return len(z_range) == 2 and all(isinstance(r, (tuple, list)) for r in z_range)
 
 
 def _zkey(z_range):

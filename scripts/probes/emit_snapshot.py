@@ -1,7 +1,8 @@
 """sha256 of the emitted HIP source of every default launch plan over a matrix of workloads, shapes, boundary modes
 and pointer-alignment classes (no GPU: the plan selection of ``HipStencilKernel._plan_march`` runs on stand-in
-tensors, the compile step is skipped). Used to show that a refactor of the emitters leaves every default kernel
-byte-identical:
+tensors, the compile step is skipped). The by-hand check of emitted TEXT: it shows that a refactor of the emitters
+leaves every default kernel byte-identical. Which plan a launch gets is pinned by the committed
+``tests/test_march_plan.py`` (``tests/golden/march_plan.json``), not here:
 
 python scripts/probes/emit_snapshot.py > before.txt; (edit); python scripts/probes/emit_snapshot.py | diff before.txt -
 """
