@@ -24,8 +24,8 @@ in ``scripts/probes/rowblock27r.py`` (``profiles/r03_band_*.log``).
 """
 import numpy as np
 
-from .hip_emitter import (PRELUDE, MarchConfig, _field_params, _scalar_params, _ws_plane_base, extra_params,
-                          halo_wait_lines, start_signal_lines, zsum_plan)
+from .hip_emitter import (PRELUDE, MarchConfig, extra_params, field_params, halo_wait_lines, scalar_params,
+                          start_signal_lines, ws_plane_base, zsum_plan)
 from .printer import KernelExprPrinter
 
 __all__ = ['band_plans', 'band_geometry', 'band_choice', 'band_esize', 'emit_band']
@@ -53,8 +53,6 @@ def band_plans(ir):
         w = {}
         for dz, terms in pl['lin'].items():
             for coeff, f, dy, dx, k in terms:
-                if (f is not stencil[0] and f.name != stencil[0].name) or k != 0:
-                    return None
                 w[(dz, dy, dx)] = w.get((dz, dy, dx), 0) + coeff
         out.append(dict(field=pl['field'], w=w))
     return out
@@ -203,13 +201,13 @@ def emit_band(ir, name, cfg):
             return f'(_Float16){A(si, s, o, q % 4)}.{"x" if q < 4 else "y"}'
         return A(si, s, o, q)
 
-    params = _field_params(ir)
+    params = field_params(ir)
     params += [f'const {et}* __restrict__ hlo_{S.name}', f'const {et}* __restrict__ hhi_{S.name}']
     params += ['const int Z', 'const int Y', 'const int X', 'const int zlo', 'const int zhi', 'const int ylo',
                'const int yhi', 'const int xlo', 'const int xhi', 'const int zc', 'const int zstep', 'const int ntx',
                'const int nty']
     params += extra_params(cfg)
-    params += _scalar_params(ir)
+    params += scalar_params(ir)
     L = [PRELUDE, 'typedef unsigned u32x4 __attribute__((ext_vector_type(4)));',
          'typedef unsigned u32x3 __attribute__((ext_vector_type(3)));', 'typedef unsigned u32x2 __attribute__((ext_vector_type(2)));']
     L.append(f'// band schedule: {TY}-row bands of full {X}-element rows, {R} rows x {VE} cells per lane, {NCT // 64} '
@@ -279,7 +277,7 @@ def emit_band(ir, name, cfg):
             L.append(f'      vo1[i] = ok ? 2 * s1 + 16 * pc : 0x7ffffff0;')
         L.append('    }')
         L.append('    auto issue = [&](const int q, const int slot) {')
-        L.append(f'      const {et}* pb = {_ws_plane_base(S, 1, "q")};')
+        L.append(f'      const {et}* pb = {ws_plane_base(S, 1, "q")};')
         if bo:
             L.append('      const int pp = hpar(pb);')
             L.append(f'      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(pb ? pb - pp : '
@@ -322,7 +320,7 @@ def emit_band(ir, name, cfg):
             # plane j has landed: zeros over the image columns past each row's last element (X + the row's parity .. XP)
             nz = XP - X
             L.append('      {')
-            L.append(f'        const int ppj = hpar({_ws_plane_base(S, 1, "(zb - 1 + j)")});')
+            L.append(f'        const int ppj = hpar({ws_plane_base(S, 1, "(zb - 1 + j)")});')
             L.append(f'        {et}* img = lds + (j % {NS}) * {SLOT};')
             L.append(f'        for (int i = lane; i < {(TY + 2) * nz}; i += 64) {{')
             L.append(f'          const int rr = i / {nz}, c = i - rr * {nz}, pos = {X} + (ppj ^ ((y0 - 1 + rr) & 1)) + c;')
@@ -376,7 +374,7 @@ def emit_band(ir, name, cfg):
 
         def load(sname, q):
             B = ['    {',
-                 f'      const {et}* pb = {_ws_plane_base(S, 1, "(" + q + ")")};',
+                 f'      const {et}* pb = {ws_plane_base(S, 1, "(" + q + ")")};',
                  f'      a{sname} = pb ? (int)((unsigned long long)pb & 3ull) : 0;',
                  f'      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(pb ? '
                  f'(const char*)pb - a{sname} : (const char*)f_{S.name}), (short)0, pb ? (int)((a{sname} + YX * {es} + 3) '
@@ -766,7 +764,7 @@ def emit_band(ir, name, cfg):
             # v_perm selectors: input row parity = plane parity ^ (y0 - 1 + row) & 1, y0 and R even -> odd rows r of
             # the lane take the plane's parity (selA), even rows the other one (selB); 0x05040302 = elements shifted
             # by one (the row was loaded one element early), 0x07060504 = the dword as it is
-            B += [f'{ind}  const int ppq = hpar({_ws_plane_base(S, 1, "(zb - 1 + jj)")});',
+            B += [f'{ind}  const int ppq = hpar({ws_plane_base(S, 1, "(zb - 1 + jj)")});',
                   # (scalar arithmetic, not selects: a select becomes a 64-bit lane mask per unrolled step)
                   f'{ind}  const unsigned selA = 0x05040302u + (unsigned)ppq * 0x02020202u, '
                   'selB = 0x07060504u - (unsigned)ppq * 0x02020202u;']

@@ -14,10 +14,10 @@ import os
 
 import numpy as np
 
-from . import hip_runtime as rt
+from . import hip_emitter as he, hip_runtime as rt
 from .hip_band import band_geometry, emit_band
-from .hip_emitter import (MarchConfig, emit_generic, emit_march, emit_pointwise, emit_zsum, march_geometry, ncomp,
-                          ws_geometry, zsum_plan)
+from .hip_emitter import (MarchConfig, emit_generic, emit_march, emit_pointwise, emit_zero_border, emit_zsum, magic_u32,
+                          march_geometry, ncomp, ws_geometry, zsum_plan)
 from .march_plan import (PROBE_KEYS, PROBE_KNOBS, TILE_KEYS, align_class as _align_class,  # noqa: F401 (re-exports)
                          default_march_config, is_pair as _is_pair, march_extents, resolve_march, ws_fallback_config)
 
@@ -299,7 +299,6 @@ class HipStencilKernel:
         fns = self.function(('pointwise',), device)
         n = int(np.prod(shape))
         aligned = all(t.data_ptr() % 32 == 0 for t in tensors)
-        from . import hip_emitter as he
         per_block = 256 * (4 * he.POINTWISE_UNROLL if aligned else 1)
         cap = (he.POINTWISE_MAX_BLOCKS or 2 ** 31 - 1) if aligned else 256 * 16
         blocks = max(1, min(math.ceil(n / per_block), cap))
@@ -308,7 +307,6 @@ class HipStencilKernel:
                      len(tensors), 0, [n])
 
     def _plan_generic(self, tensors, shape, device):
-        from .hip_emitter import magic_u32
         ir = self.ir
         if ir.periodic and any(r >= int(n) for r, n in zip(ir.radius, shape)):
             raise ValueError(f'periodic kernel: stencil radius {ir.radius} must be below the extent {shape}')
@@ -552,7 +550,6 @@ def zero_border(t, bounds, ncomp=1, stream=None, x=True, zy=True):
     ends of the rows (written by an ``x_border`` launch), ``zy=False`` does only those."""
     import struct
     torch = _torch()
-    from .hip_emitter import emit_zero_border
     nd = len(bounds)
     shape = [int(s) for s in t.shape[:nd]]
     bounds = [(int(a), int(b)) for a, b in bounds]

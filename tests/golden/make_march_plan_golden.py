@@ -1,7 +1,7 @@
 """Generate ``tests/golden/march_plan.json`` (run: python tests/golden/make_march_plan_golden.py): what the march
 planner decides, over a matrix of kernels, shapes, vector widths, tile overrides, environment switches, pointer
 alignments and launch options. No GPU: the planner is host code; compile and residency are stubbed (``function`` and
-``_resident_slots`` return None) as in ``scripts/probes/emit_snapshot.py``.
+``_resident_slots`` return None). ``make_emit_golden.py`` pins the emitted source of every plan made here.
 
 Two kinds of rows, both entered only through names that keep their signature:
 
@@ -35,7 +35,7 @@ ENV_KEYS = ('PSAD_MARCH', 'PSAD_BAND', 'PSAD_BAND_UNALIGNED', 'PSAD_XO', 'PSAD_M
 
 
 class FakeTensor:
-    """What ``_plan_march`` reads of a tensor: pointer, shape, dtype, contiguity (``emit_snapshot.FakeTensor``)."""
+    """What ``_plan_march`` reads of a tensor: pointer, shape, dtype, contiguity."""
     is_cuda = True
 
     def __init__(self, shape, dtype, ptr):
@@ -100,7 +100,7 @@ def _wide(radius, dts):
                                     c[-R, R, -R] * c[R, 0, R] * a[0, -R, 0]})
 
 
-# (name, builder, the shapes of scripts/probes/emit_snapshot.py for this kernel)
+# (name, builder, the benchmark shapes of this kernel)
 CASES = [
     ('diffusion7', W.diffusion_7pt, [(1024,) * 3, (512,) * 3, (768,) * 3, (128, 1024, 1024), (255,) * 3, (64, 300, 261)]),
     ('diffusion7_f16', lambda: W.diffusion_7pt(dtype='float16'), [(768,) * 3, (511,) * 3, (510,) * 3, (512, 512, 520)]),
