@@ -49,6 +49,10 @@ class AutoDiffBoundaryHandling(str, Enum):
     ``'valid'``: not implemented by the reference either (``_autodiff.py:246-247``).
     ``'periodic'``: (extension, not in the reference) reads and offset writes wrap around the domain,
     every cell is written — the lattice Boltzmann step's periodic lattice (``lbm/``) without ghost layers.
+    On the GPU, 3-D stencils on scalar fields that store at offset 0 run on the march schedules (the LDS-DMA loader
+    fills each plane image from wrapped source offsets) where the rows are whole 16-byte pieces and the pointers
+    16-byte aligned, and split into z-slabs with a wrap-around exchange (``zslab.ZSlabOp``); everything else — 2-D,
+    vector fields, offset stores, other row pitches — runs one thread per cell.
     """
     NONE = None
     ZEROS = 'zeros'

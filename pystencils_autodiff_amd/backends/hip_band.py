@@ -152,6 +152,8 @@ def band_choice(X, nstore=1, es=2, pad=0, reg=0, idle=False, star=False, wide16=
 def emit_band(ir, name, cfg):
     """HIP source of the band kernel (signature identical to the march / zsum kernels: fields, 2 halo pointers
     per stencil field, Z Y X zlo zhi ylo yhi xlo xhi zc zstep ntx nty, scalars)."""
+    if ir.periodic:
+        raise ValueError('the band schedule has no periodic form (its row ends and halo planes are zero-filled)')
     plans = band_plans(ir)
     if plans is None:
         raise ValueError('kernel is not eligible for the band schedule')

@@ -19,7 +19,8 @@ from .hip_band import band_geometry, emit_band
 from .hip_emitter import (MarchConfig, emit_generic, emit_march, emit_pointwise, emit_zero_border, emit_zsum, magic_u32,
                           march_geometry, ncomp, ws_geometry, zsum_plan)
 from .march_plan import (PROBE_KEYS, PROBE_KNOBS, TILE_KEYS, align_class as _align_class,  # noqa: F401 (re-exports)
-                         default_march_config, is_pair as _is_pair, march_extents, resolve_march, ws_fallback_config)
+                         default_march_config, is_pair as _is_pair, march_extents, periodic_march_config, resolve_march,
+                         ws_fallback_config)
 
 __all__ = ['HipStencilKernel', 'default_march_config']
 
@@ -50,14 +51,20 @@ class HipStencilKernel:
             return 'generic'               # an iteration_slice: any rectangular subset, bound-checked reads
         if ir.pointwise:
             return 'generic' if ir.has_index_dims else 'pointwise'
-        if ir.periodic:
-            return 'generic'                   # wrapped reads: one thread per cell
         taps = {}
         for r in ir.reads:
             taps.setdefault(r.field, set()).add(r.offsets)
         if ir.stencil_fields and not ir.has_index_dims and all(len(taps.get(f, ())) == 1 for f in ir.stencil_fields):
             # every stencil field read at ONE offset (pull-streaming lattice Boltzmann: component i at -c_i):
             # staging planes in LDS buys no reuse, the one-thread-per-cell schedule streams each component
+            return 'generic'
+        if ir.periodic:
+            # wrapped reads: 3-D scalar-field stencils storing at offset 0 take the march schedules with wrapped
+            # LDS-DMA plane loads (where a launch's rows allow, march_plan.resolve_march); everything else — 2-D,
+            # vector fields, offset stores — one thread per cell
+            if ir.ndim == 3 and ir.stencil_fields and not ir.has_index_dims and \
+                    all(all(o == 0 for o in s[1]) for s in ir.stores) and len({f.dtype for f in ir.fields}) == 1:
+                return 'march'
             return 'generic'
         if ir.ndim in (2, 3) and all(all(o == 0 for o in s[1]) for s in ir.stores) and \
                 len({f.dtype for f in ir.fields}) == 1:
@@ -106,6 +113,9 @@ class HipStencilKernel:
             fixed = [f for f in self.ir.fields if f.has_fixed_shape]
             if fixed:
                 shape = tuple(int(x) for x in fixed[0].spatial_shape)
+            if self.ir.periodic:
+                cfg = periodic_march_config(self.ir, self._vec_elems(), shape, self.kernel.tuning)
+                return ('march', cfg) if cfg is not None else ('generic',)
             return ('march', self._march_cfg(self._vec_elems(), shape))
         return (s,)
 
@@ -149,7 +159,8 @@ class HipStencilKernel:
 
         ``x_border=True`` asks the zsum schedule to also store zeros at x outside the iteration bounds of
         the rows it writes (returns True if the launch did). ``halos`` = ``{field: (lo_planes, hi_planes)}``: tensors holding the RZ planes just
-        below plane 0 / above plane Z-1 of a stencil field (``None`` = zeros); ``z_range``
+        below plane 0 / above plane Z-1 of a stencil field (``None`` = zeros, or for a periodic kernel its own far
+        planes); ``z_range``
         restricts the written planes of axis 0 — ``(lo, hi)``, or two disjoint ranges of equal
         length ``((lo0, hi0), (lo1, hi1))`` written by ONE launch (the two slab faces; both:
         z-slab decomposition, ``zslab.py``). ``z_limits=(lo, hi)`` replaces the kernel's own axis-0
@@ -413,6 +424,8 @@ class HipStencilKernel:
     def _plan_march(self, tensors, halo_list, shape, device, z_range, x_border=False, z_limits=None,
                     start_signal=False, halo_wait=False):
         ir = self.ir
+        if ir.periodic and any(r >= int(n) for r, n in zip(ir.radius, shape)):
+            raise ValueError(f'periodic kernel: stencil radius {ir.radius} must be below the extent {shape}')
         stencil = ir.stencil_fields
         by_name = {f.name: t for f, t in zip(ir.fields, tensors)}
         read = [by_name[f.name] for f in stencil] + [h for h in halo_list if h is not None]

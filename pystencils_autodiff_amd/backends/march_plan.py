@@ -5,7 +5,9 @@ alignment classes, tile overrides and the environment (no torch, no tensor, no d
 class, class defaults, override repairs, the row-band schedule (``_band_config``), fit to the shape, fit to the LDS,
 the workgroup map. ``resolve_march`` adds what depends on one launch (the vector width and row-alignment route its
 pointers allow, 32-bit plane offsets, border stores, band store masks, start signal, halo wait) and returns the final
-``MarchConfig``, or None for the one-thread-per-cell schedule. ``tests/test_march_plan.py`` pins both.
+``MarchConfig``, or None for the one-thread-per-cell schedule. ``tests/test_march_plan.py`` pins both. Periodic kernels
+take their own, narrower path (``periodic_march_config``, ``_resolve_periodic``: LDS-DMA loader tiles on rows of whole
+16-byte pieces only), pinned by ``tests/test_periodic_march.py``.
 
 Environment: ``PSAD_MARCH="CX=..,NR=.."`` (tile overrides, ``_overrides``) and the switches read by ``_switch``:
 ``PSAD_BAND=0`` (no row-band schedule), ``PSAD_BAND_UNALIGNED=0`` (none on rows of other pitches than 16 bytes),
@@ -572,12 +574,63 @@ def _route(ir, plan, shape, stencil_align, all_align, restricted):
     return plan(ve, ve == ve0 and all_align >= 4 and offsets32)
 
 
+def periodic_march_config(ir, ve, shape=None, tuning=None):
+    """The tile of a periodic kernel (3-D, scalar fields): the stencil-class default without the row band, where it
+    ends on an LDS-DMA loader (``ws_geometry``: the wrapped plane loads are the loader's,
+    ``hip_emitter._ws_piece_offsets``) — else, unless the overrides set ``WS`` themselves, the same tile with the loader on
+    (fp32 / fp64 box stencils, whose 'zeros' default is the register-prefetch form), and for fp16 storage last with
+    ``CX=4`` as well: the half-precision rings' lanes own quads / pairs of x-adjacent cells, which rows narrower than
+    the tile (or a ``CX`` override) would drop; a tile wider than the rows only loads wrapped duplicates — or None."""
+    tries = [{}] if 'WS' in _overrides(tuning) else [{}, {'WS': True}]
+    if any(storage_ctype(f) == '_Float16' for f in ir.stencil_fields):
+        tries.append({'WS': True, 'CX': 4})
+    for extra in tries:
+        try:
+            cfg = default_march_config(ir, ve, shape, {**dict(tuning or {}), **extra}, band=False)
+        except ValueError:
+            if not extra:
+                raise
+            continue
+        ws = ws_geometry(ir, cfg)
+        if ws is not None and ws['lds_bytes'] <= LDS_MAX and not (cfg.BAND or cfg.XM or cfg.XO):
+            return cfg
+    return None
+
+
+def _resolve_periodic(ir, tuning, shape, stencil_align):
+    """``resolve_march`` for a periodic kernel: ``(config, None)``, or ``(None, why)`` where the launch cannot end on
+    an LDS-DMA loader with rows of whole 16-byte pieces (never the band, XM / XO, narrower vectors or the
+    register-prefetch fallback: those zero-fill what lies outside the domain)."""
+    esize = ir.fields[0].dtype.itemsize
+    ve, X = 16 // esize, int(shape[-1])
+    if ir.ndim != 3 or ir.has_index_dims:
+        return None, 'periodic kernels march only over 3-D scalar fields'
+    if (X * esize) % 16:
+        return None, f'the row pitch of {X * esize} bytes is not a multiple of 16 bytes'
+    if stencil_align < 4:
+        return None, f'a stencil field or halo pointer is only {1 << stencil_align}-byte aligned (16 bytes needed)'
+    if int(np.prod(shape[1:])) * esize >= OFFSET_MAX:
+        return None, "a plane lies beyond the LDS-DMA loader's 32-bit offsets"
+    cfg = periodic_march_config(ir, ve, shape, tuning)
+    if cfg is None:
+        return None, 'no LDS-DMA loader tile applies to this stencil (storage and compute types, LDS size, overrides)'
+    return cfg, None
+
+
 def resolve_march(ir, tuning, shape, stencil_align, all_align, halos=False, z_range=None, z_limits=None,
                   x_border=False, start_signal=False, halo_wait=False):
     """The ``MarchConfig`` of one launch, or None for the one-thread-per-cell schedule. ``stencil_align`` /
     ``all_align``: the lowest ``align_class`` among the stencil fields' tensors and halo planes / among all field
     tensors; ``halos``: halo planes are passed."""
     restricted = halos or z_range is not None or z_limits is not None
+    if ir.periodic:
+        cfg, why = _resolve_periodic(ir, tuning, shape, stencil_align)
+        if cfg is None:
+            if restricted or start_signal or halo_wait:
+                raise ValueError('halo planes / z ranges / start signals are only supported by the march schedule, '
+                                 f'which this launch of a periodic kernel cannot take: {why}')
+            return None
+        return replace(cfg, SIG=bool(start_signal), HWAIT=bool(halo_wait))
     cfg = _route(ir, lambda ve, band: default_march_config(ir, ve, shape, tuning, band=band), shape, stencil_align,
                  all_align, restricted)
     if cfg is None:

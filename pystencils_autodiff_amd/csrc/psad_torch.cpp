@@ -195,7 +195,8 @@ struct Exchange {
     std::vector<void*> recv_lo, recv_hi;  // receive buffers (nullptr: no neighbour on that side)
     std::vector<size_t> bytes;
     int peer_lo = -1, peer_hi = -1;
-    bool loopback = false;                // one-rank communicator: both faces to itself (periodic z)
+    bool loopback = false;                // both neighbours are one rank (a one-rank communicator: both faces to
+                                          // itself; two ranks of a periodic lattice): the faces go out swapped
     // the two cross-stream orderings as stream memory operations (hipStreamWriteValue32 / hipStreamWaitValue32 on a
     // signal-memory word with a sweep counter; PSAD_SLAB_SYNC=event: event record + wait instead)
     // one HSA signal per ordering (signal memory is allocated 8 bytes at a time)
@@ -303,8 +304,9 @@ void run_sweep(const Sweep& w, const std::vector<at::Tensor>& table, const std::
             char* base = static_cast<char*>(table[ex.slot[i]].data_ptr());
             send_lo[i] = base;
             send_hi[i] = base + ex.last_off[i];
-            // RCCL pairs a peer's sends and receives in issue order: on a loopback communicator the lower halo
-            // receives the far (upper) face, as with real neighbours — a periodic z boundary
+            // RCCL pairs a peer's sends and receives in issue order: where both neighbours are the same rank (loopback,
+            // or the two ranks of a periodic lattice) the lower halo receives the far (upper) face, as with two
+            // distinct neighbours — a periodic z boundary
             if (ex.loopback) std::swap(send_lo[i], send_hi[i]);
         }
         int rc = psad_halo_exchange(ex.comm, static_cast<int>(n), send_lo.data(), ex.recv_lo.data(), send_hi.data(),

@@ -15,7 +15,7 @@ the MI355X layer's scale-out for the 3-D configs (BASELINE configs 4 and 5):
   of host time per exchange) remains the path for ``gloo`` and for
   ``PSAD_HALO=torch``. Rank 0's lower and rank ``P-1``'s upper
   halos stay absent, which the kernel reads as zeros — the ``'zeros'``
-  boundary of the undivided domain;
+  boundary of the undivided domain (``'periodic'`` kernels: those two ranks are neighbours too);
 * the exchange overlaps the interior planes: the march kernel first writes
   planes ``[RZ, Zl-RZ)`` (no halo needed) while the faces are in flight, then,
   after the receive completes, the ``RZ`` planes at each end (one launch for both
@@ -132,6 +132,11 @@ class RcclHalo:
             self.comm = None
 
 
+def _writes_all(ir):
+    """The kernel writes every local plane ('zeros', periodic, or no neighbour access): no global z limits."""
+    return bool(ir.zeros or ir.periodic or ir.ghost_layers == 0)
+
+
 def slab_bounds(n, world, rank):
     """``[lo, hi)`` of axis 0 owned by ``rank``."""
     base, rem = divmod(n, world)
@@ -139,15 +144,19 @@ def slab_bounds(n, world, rank):
     return lo, lo + base + (1 if rank < rem else 0)
 
 
-def exchange_halos(t, rz, group=None, bufs=None):
+def exchange_halos(t, rz, group=None, bufs=None, periodic=False):
     """Send the first/last ``rz`` planes of ``t`` to the lower/upper neighbour and receive theirs.
 
     Returns ``(works, lo_halo, hi_halo)``; halos are ``None`` at the global boundary. The
-    receive buffers may be passed in (``bufs=(lo, hi)``) to avoid reallocation.
+    receive buffers may be passed in (``bufs=(lo, hi)``) to avoid reallocation. ``periodic``: the neighbours wrap
+    (rank 0's lower one is the last rank); with two ranks both are the same rank, whose sends and receives match
+    in posting order — last planes out, lower halo in, first planes out, upper halo in.
     """
+    if rz == 0 or not dist.is_initialized():
+        return [], None, None
     rank = dist.get_rank(group)
     world = dist.get_world_size(group)
-    if rz == 0 or world == 1:
+    if world == 1:
         return [], None, None
     if t.shape[0] < rz:
         raise ValueError(f"slab of {t.shape[0]} planes is thinner than the stencil radius {rz}")
@@ -155,16 +164,19 @@ def exchange_halos(t, rz, group=None, bufs=None):
     lo = hi = None
     ops = []
     peer = (lambda r: dist.get_global_rank(group, r)) if group is not None else (lambda r: r)
-    if rank > 0:
+    first, last = t[:rz], t[-rz:]
+    if periodic and world == 2:
+        first, last = last, first           # one peer on both sides: its first receive is its lower halo
+    if rank > 0 or periodic:
         lo = bufs[0] if bufs is not None and bufs[0] is not None else torch.empty(plane_shape, dtype=t.dtype,
                                                                                  device=t.device)
-        ops.append(dist.P2POp(dist.isend, t[:rz].contiguous(), peer(rank - 1), group))
-        ops.append(dist.P2POp(dist.irecv, lo, peer(rank - 1), group))
-    if rank < world - 1:
+        ops.append(dist.P2POp(dist.isend, first.contiguous(), peer((rank - 1) % world), group))
+        ops.append(dist.P2POp(dist.irecv, lo, peer((rank - 1) % world), group))
+    if rank < world - 1 or periodic:
         hi = bufs[1] if bufs is not None and bufs[1] is not None else torch.empty(plane_shape, dtype=t.dtype,
                                                                                  device=t.device)
-        ops.append(dist.P2POp(dist.isend, t[-rz:].contiguous(), peer(rank + 1), group))
-        ops.append(dist.P2POp(dist.irecv, hi, peer(rank + 1), group))
+        ops.append(dist.P2POp(dist.isend, last.contiguous(), peer((rank + 1) % world), group))
+        ops.append(dist.P2POp(dist.irecv, hi, peer((rank + 1) % world), group))
     if ops and t.is_cuda and dist.get_backend(group) == 'gloo':
         # gloo moves host memory only: stage through the CPU (tests / debugging, not the RCCL path)
         staged = [dist.P2POp(op.op, op.tensor.cpu() if op.op is dist.isend else torch.empty_like(op.tensor, device='cpu'),
@@ -191,6 +203,12 @@ class ZSlabOp:
     0 — and ``[g, N-g)`` of the others — is written; the untouched border keeps what the caller
     allocated). Interior-only slabs need their place in the global domain: ``z_offset`` / ``global_z``,
     else gathered once from every rank's slab extent (collective, on the first sweep).
+
+    ``'periodic'`` kernels (3-D scalar fields on the march schedule, or the C kernels): every rank has two
+    neighbours, ``(rank ± 1) mod world``, and receives both halos; x and y wrap inside the kernel. With two ranks
+    both neighbours are one rank, whose sends and receives match in posting order: the faces go out swapped (last
+    planes out, lower halo in, first planes out, upper halo in), as on the one-rank loopback communicator. One
+    rank without a communicator exchanges nothing: the kernel wraps z itself.
     """
 
     def __init__(self, autodiff_op, use_cuda=True, group=None, z_offset=None, global_z=None):
@@ -203,10 +221,8 @@ class ZSlabOp:
         for k in self.kernels.values():
             if k.ir.ndim != 3 and k.ir.ndim != 2:
                 raise ValueError('z-slab decomposition needs 2-D or 3-D fields')
-            if k.ir.periodic:
-                # a periodic lattice needs a wrap-around exchange between the first and last rank (and the
-                # kernels' own wrapped reads disabled along z): not built
-                raise NotImplementedError("z-slab decomposition of boundary_handling='periodic' kernels")
+        # periodic kernels: the exchange wraps around (every rank has two neighbours), x and y wrap in the kernels
+        self.periodic = any(k.ir.periodic for k in self.kernels.values())
         self._span = {} if z_offset is None or global_z is None else None
         self._fixed_span = None if self._span is not None else (int(z_offset), int(global_z))
         self._bufs = {}
@@ -294,7 +310,7 @@ class ZSlabOp:
         """Local ``[lo, hi)`` of the planes this rank writes: all of them under ``'zeros'``, the part of
         the global interior ``[g, Z-g)`` under ``boundary_handling=None``."""
         ir = kernel.ir
-        if ir.zeros or ir.ghost_layers == 0:
+        if _writes_all(ir):
             return 0, zl
         z0, Z = self.span(zl)
         g = ir.ghost_layers
@@ -355,12 +371,17 @@ class ZSlabOp:
             # the GPU kernels take one halo pair per fzyx component; the CPU path ghosts whole slabs
             for name, t in (self._units(f, kwargs[f.name]) if self.use_cuda else [(f.name, kwargs[f.name])]):
                 key = (which, name, rz, t.dtype, tuple(t.shape[1:]), t.device)
-                works, lo, hi = exchange_halos(t, rz, self.group, self._bufs.get(key))
+                works, lo, hi = exchange_halos(t, rz, self.group, self._bufs.get(key), periodic=ir.periodic)
                 self._bufs[key] = (lo, hi)
                 pending += works
                 halos[name] = (lo, hi)
         # interior-only kernels always take the limits (their own bounds would skip the slab's end planes)
-        kz = None if (ir.zeros or ir.ghost_layers == 0) else zlim
+        kz = None if _writes_all(ir) else zlim
+        if ir.periodic and all(h == (None, None) for h in halos.values()):
+            # one rank without a communicator: no exchange and no halos, the kernel wraps z itself
+            if zlim[1] > zlim[0]:
+                k.compile()(**kwargs)
+            return
         if self.use_cuda:
             compiled = k.compile()
             if split:
@@ -377,7 +398,8 @@ class ZSlabOp:
         # carries g >= rz planes per side so that its own interior covers every local plane
         for w in pending:
             w.wait()
-        pad = rz if (ir.zeros or ir.ghost_layers == 0) else max(rz, ir.ghost_layers)
+        # (a periodic kernel wraps x and y itself; its z wrap on the copy only touches the discarded ghost planes)
+        pad = rz if _writes_all(ir) else max(rz, ir.ghost_layers)
         ghosted = dict(kwargs)
         outs = {f.name: kwargs[f.name] for f in ir.fields_written}
         read_names = {r.field.name for r in ir.reads}
@@ -402,11 +424,19 @@ class ZSlabOp:
             if pad and b > a:
                 t[a:b].copy_(ghosted[name][pad + a:pad + b])
 
-    @staticmethod
-    def _peers(halo):
+    def _peers(self, halo):
         if halo.loopback:
             return 0, 0
+        if self.periodic:
+            return (halo.rank - 1) % halo.world, (halo.rank + 1) % halo.world
         return (halo.rank - 1 if halo.rank > 0 else -1), (halo.rank + 1 if halo.rank < halo.world - 1 else -1)
+
+    def _swap_faces(self, halo):
+        """RCCL pairs one peer's sends and receives in issue order: where both neighbours are the same rank (a
+        loopback communicator; two ranks of a periodic lattice) the faces go out swapped, so that the peer's first
+        receive — its lower halo — gets this rank's last planes."""
+        peer_lo, peer_hi = self._peers(halo)
+        return bool(halo.loopback) or (peer_lo == peer_hi and peer_lo >= 0)
 
     def _face_planes(self, halo, named, rz):
         """Send / receive pointers of the RZ boundary planes of each ``(name, slab)`` and the receive
@@ -421,9 +451,9 @@ class ZSlabOp:
             lo, hi, nbytes, last_off = self._recv_bufs(halo, name, rz, tuple(t.shape), t.dtype, t.device)
             first = t.data_ptr()
             last = first + last_off
-            if halo.loopback:
-                # RCCL pairs a peer's sends and receives in issue order: swap the faces so that, as
-                # with real neighbours, the lower halo receives the far (upper) face — periodic z
+            if self._swap_faces(halo):
+                # swap the faces so that, as with two distinct neighbours, the lower halo receives the far
+                # (upper) face — periodic z
                 first, last = last, first
             planes.append((first, lo.data_ptr() if lo is not None else 0, last,
                            hi.data_ptr() if hi is not None else 0, nbytes))
@@ -483,7 +513,7 @@ class ZSlabOp:
         compiled = k.compile()
         zl = kwargs[k.ir.fields_written[0].name].shape[0]
         zlim = (0, zl) if zlim is None else zlim
-        kz = None if (k.ir.zeros or k.ir.ghost_layers == 0) else zlim
+        kz = None if _writes_all(k.ir) else zlim
         inner, faces = self._launches(zl, rz, zlim)
         if inner:
             compiled(z_range=inner, z_limits=kz, **kwargs)  # interior overlaps the exchange
@@ -503,11 +533,11 @@ class ZSlabOp:
         comps = tuple(int(n) for n in f.index_shape) if f is not None and f.index_dimensions else ()
         shape = tuple(like.shape[:sdim]) + comps
         soa = f is not None and f.is_soa
-        zero = read or (not ir.zeros and ir.ghost_layers and not like.is_cuda)
+        zero = read or (not _writes_all(ir) and not like.is_cuda)
         factory = torch.zeros if zero else torch.empty
         t = _soa_empty(shape, sdim, factory, dtype, like.device) if soa else \
             factory(shape, dtype=dtype, device=like.device)
-        if not zero and not ir.zeros and ir.ghost_layers:
+        if not zero and not _writes_all(ir):
             from .backends.hip_kernel import zero_border
             bounds = ir.iteration_bounds(tuple(like.shape[:sdim]))
             bounds[0] = self.z_limits(kernel, like.shape[0])
@@ -648,7 +678,7 @@ class _NativeSlab:
         zop = self.zop
         fk, bk = zop.kernels['forward'], zop.kernels['backward']
         for k in (fk, bk):
-            if not (k.ir.zeros or k.ir.ghost_layers == 0):
+            if not _writes_all(k.ir):
                 return None                 # interior-only kernels: border fills and global z limits
             if any(f.is_soa for f in k.ir.fields):
                 return None                 # fzyx vector fields: per-component halos and strided slabs
@@ -732,7 +762,7 @@ class _NativeSlab:
             if any(f is None for f in face_l):
                 return None
             peer_lo, peer_hi = zop._peers(halo)
-            ex = (ex_slot, ex_off, rlo, rhi, nbytes, peer_lo, peer_hi, bool(halo.loopback))
+            ex = (ex_slot, ex_off, rlo, rhi, nbytes, peer_lo, peer_hi, zop._swap_faces(halo))
             return inner_l, face_l, ex
 
         def allocs(outs, read, kw):

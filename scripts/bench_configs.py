@@ -401,6 +401,14 @@ def main():
         ('veclaplace7_f32_384^3x3', lambda: W.vector_laplace_7pt(), (384, 384, 384, 3), torch.float32, 'zeros', 1,
          24, 24),
     ]
+    # periodic boxes (wrapped LDS-DMA plane loads; no row band): the same builders with bh='periodic'
+    cfgs += [
+        ('diffusion7_f32_512^3_periodic', lambda: W.diffusion_7pt(), (512, 512, 512), torch.float32, 'periodic', 1,
+         8, 8),
+        ('stencil27_f16_768^3_periodic', lambda: W.stencil_27pt(), (768, 768, 768), torch.float16, 'periodic', 1, 4, 4),
+        ('varcoef7_f32_512^3_periodic', lambda: W.varcoef_diffusion_7pt(), (512, 512, 512), torch.float32, 'periodic',
+         2, 12, 20),
+    ]
     # row pitch: extents that are not a multiple of 16 bytes next to their power-of-two neighbours (VERDICT r03 item
     # 5: within 15 %)
     for n in (510, 512):
