@@ -37,6 +37,7 @@ import sympy as sp
 from .. import ps
 from ..autodiff import AutoDiffOp
 from ._lattice_kernels import LatticeKernels, fix_cells, neighbour_mask
+from ._lattice_source import density_links_message
 from ._method import LBStencil
 from .boundaries import (AdjointBoundaryCondition, AdjointNoSlip, Boundary, BoundaryHandling, LBMethodView,  # noqa: F401
                          NoSlip, link_form)
@@ -286,7 +287,11 @@ class AutoDiffLatticeBoltzmannStep:
                                and self._lattice_force is not None
                                and os.environ.get('PSAD_LBM_LATTICE', '1') != '0'
                                and extras_ok and trt_ok and self._omega_of is not None
-                               and np.dtype(src.dtype.numpy_dtype) in (np.float32, np.float64)
+                               and np.dtype(src.dtype.numpy_dtype) in (np.float16, np.float32, np.float64)
+                               # (float16 pdfs with a force / ω field: the AutoDiffOp kernels — the lattice kernels
+                               # would accumulate the field's adjoint over the steps in float16)
+                               and (np.dtype(src.dtype.numpy_dtype) != np.float16 or
+                                    (self._force_field is None and self._omega_field is None))
                                and (self._force_field is None or
                                     self._force_field.dtype.numpy_dtype == src.dtype.numpy_dtype)) else None
         self._boundary = BoundaryHandling(self.domain_size, on_change=self._flags_changed)
@@ -430,7 +435,16 @@ class AutoDiffLatticeBoltzmannStep:
                     constant_fields=list(self._autodiff_args['constant_fields'] or []) + ['indexVector']))
         elif not isinstance(adjoint_boundary_condition, (AdjointNoSlip, AdjointBoundaryCondition)):
             raise NotImplementedError(f'adjoint boundary {adjoint_boundary_condition!r}')
-        link_form(boundary_condition, adjoint_boundary_condition, self._bc_method)   # the kernels' form, or raise
+        kind, form = link_form(boundary_condition, adjoint_boundary_condition, self._bc_method)   # or raise
+        # links that read a density (density-weighted, link programs, neighbour links) are built for plain float32 /
+        # float64 pdfs only (``LatticeSource``)
+        reads_density = any(p is not None for p in form) if kind != 'affine' else \
+            any(len(t) > 3 and (t[3] != 0 or t[4] != 0) for t in form)
+        if reads_density:
+            for on, what in ((getattr(self._update_rule, 'zero_centered', False), 'zero_centered pdfs'),
+                             (np.dtype(self.pdf_field.dtype.numpy_dtype) == np.float16, 'float16 pdfs')):
+                if on:
+                    raise NotImplementedError(density_links_message(what, f'boundary {boundary_condition!r}'))
         self._boundary.set_boundary(boundary_condition, slice_obj, mask_callback=mask_callback, mask_array=mask_array,
                                     adjoint=adjoint_boundary_condition)
 
@@ -509,7 +523,8 @@ class AutoDiffLatticeBoltzmannStep:
                 self.method, getattr(self._update_rule, 'compressible', False), self.pdf_field.dtype.numpy_dtype,
                 walls, self._target, links, *self._lattice_force, force_field=self._force_field is not None,
                 trt=self._lattice_trt, programs=programs, mrt=self._lattice_mrt,
-                omega_field=self._omega_field is not None)
+                omega_field=self._omega_field is not None,
+                zero_centered=getattr(self._update_rule, 'zero_centered', False))
         return k
 
     # -- kernels -----------------------------------------------------------------------------------
@@ -802,7 +817,8 @@ class AutoDiffLatticeBoltzmannStep:
         rho, vel = self._macroscopic_fields()
         pdf = self._pdf_io_field()
         ac = macroscopic_getter(self.method, pdf, rho, vel, getattr(self._update_rule, 'compressible', False),
-                                getattr(self._update_rule, 'force_model', None), getattr(self._update_rule, 'force', None))
+                                getattr(self._update_rule, 'force_model', None), getattr(self._update_rule, 'force', None),
+                                zero_centered=getattr(self._update_rule, 'zero_centered', False))
         op = AutoDiffOp(ac, 'LBM_GetMacroscopicValues', diff_mode='transposed', **kernel_compilation_kwargs)
         return op.create_tensorflow_op(use_cuda=self._gpu, backend=backend)
 
@@ -811,6 +827,7 @@ class AutoDiffLatticeBoltzmannStep:
         from ._method import equilibrium_setter
         rho, vel = self._macroscopic_fields()
         pdf = self._pdf_io_field()
-        ac = equilibrium_setter(self.method, pdf, rho, vel, getattr(self._update_rule, 'compressible', False))
+        ac = equilibrium_setter(self.method, pdf, rho, vel, getattr(self._update_rule, 'compressible', False),
+                                zero_centered=getattr(self._update_rule, 'zero_centered', False))
         op = AutoDiffOp(ac, 'LBM_SetMacroscopicValues', diff_mode='transposed', **kernel_compilation_kwargs)
         return op.create_tensorflow_op(use_cuda=self._gpu, backend=backend)

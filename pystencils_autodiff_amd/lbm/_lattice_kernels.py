@@ -114,8 +114,10 @@ class LatticeKernels:
     bounce-back)."""
 
     def __init__(self, stencil, compressible, dtype, walls, target, links=None, force_model=None, force=None,
-                 force_field=False, trt=None, programs=None, mrt=None, *, omega_field=False):
+                 force_field=False, trt=None, programs=None, mrt=None, *, omega_field=False, zero_centered=False):
         self.stencil = stencil
+        # the state arrays hold f_i − w_i (``LatticeSource.zero_centered``); the adjoint arrays are not shifted
+        self.zero_centered = bool(zero_centered)
         # ω read per cell from a scalar field ``[*domain]``, its adjoint accumulated by the adjoint launches
         self.omega_field = bool(omega_field)
         # MRT: (P_ω, C) relaxation matrices as float tuples (``_method.mrt_relaxation_matrices``)
@@ -126,8 +128,9 @@ class LatticeKernels:
         self.force = None if force_model is None or self.force_field else tuple(float(v) for v in force)
         self.compressible = bool(compressible)
         self.dtype = np.dtype(dtype)
-        if self.dtype not in (np.float32, np.float64):
+        if self.dtype not in (np.float16, np.float32, np.float64):
             raise NotImplementedError(f'lattice kernels for {self.dtype} pdfs')
+        # the compute type (float16 storage computes in float32; ω is passed in it)
         self.ct = 'double' if self.dtype == np.float64 else 'float'
         self.walls = bool(walls)
         self.links = links if walls else None
@@ -136,7 +139,7 @@ class LatticeKernels:
         self.spec = spec = LatticeSource(
             stencil, self.compressible, self.ct, self.walls, self.links, programs, force_model, self.force,
             self.force_field, self.trt, self.mrt, target='hip' if target == 'gpu' else 'c',
-            omega_field=self.omega_field)
+            omega_field=self.omega_field, zero_centered=self.zero_centered, half=self.dtype == np.float16)
         # density-weighted links: the adjoint takes a second pass (lbm_adj_rho) over a per-cell scratch array
         self.rho_links = spec.rho_links
         # link programs (boundaries.link_program). C: inline, a Q-component scratch array per cell and the second

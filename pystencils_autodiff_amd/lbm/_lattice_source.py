@@ -28,6 +28,13 @@ FIX_BLOCK = 64     # threads per workgroup of the fix-up kernel
 ARRAYS = dict(s='src', d='dst', g='g', o='out')       # the pdf arrays of the kernels, by the prefix of their strides
 
 
+def density_links_message(what, who='lattice kernels'):
+    """The one wording of the refusal of density-reading links (``what``: 'zero_centered pdfs' / 'float16 pdfs'), here
+    and where the step refuses the boundary before any kernel is made."""
+    return (f'{who} with {what}: links that read a density (density-weighted links, link programs, neighbour links) '
+            'are not built for them')
+
+
 def _c(v):
     """A rational / float constant as a C literal of the compute type."""
     return repr(float(v))
@@ -60,6 +67,18 @@ class LatticeSource:
     ``target`` 'hip' / 'c'. ``idx``: the type of every stride and element offset (``long long`` once an array, or the
     force field, reaches 2³¹ − 1 elements). ``addr`` 'buf' / 'ptr' (``_Addressing``). ``mode`` 'inline' / 'main' /
     'fix' (the module docstring).
+    ``half``: the pdf arrays hold IEEE half floats and ``ctype`` (``float``) is the compute type alone: HIP loads and
+    stores ``_Float16`` (2-byte buffer accesses), the C target ``uint16_t`` bits through the CPU backend's conversion
+    helpers; every store rounds to nearest-even.
+    ``zero_centered``: the STATE arrays (``src`` of every kernel, ``dst`` of the forward) hold ``δf_i = f_i − w_i``
+    (lbmpy's zero-centred storage, background density 1): every load of a pulled or bounced state value adds ``w_i``
+    in the compute type (``w_i = w_ī``, so a bounce-back and the affine links need nothing more), every store of a
+    forward result subtracts it before the cast to the storage type. The adjoint arrays ``g`` / ``out`` and the
+    obstacle cells' copies are not shifted.
+    Links that read a density (density-weighted links, link programs, neighbour links) are printed for plain pdfs of
+    the compute type only: with ``zero_centered`` or ``half`` they raise ``NotImplementedError`` (their second pass
+    and fix-up launch accumulate in the storage type, and there is no single-half atomic), as do ``half`` force / ω
+    fields (the field's adjoint would accumulate over the steps in half precision).
 
     The derived facts below follow from the fields in ``__post_init__``; a variant (another index type, addressing or
     mode) is made with ``dataclasses.replace``, never by assignment."""
@@ -79,6 +98,8 @@ class LatticeSource:
     addr: str = 'ptr'
     mode: str = 'inline'
     omega_field: bool = False
+    zero_centered: bool = False
+    half: bool = False
 
     def __post_init__(self):
         links, programs = self.links, self.programs
@@ -112,6 +133,13 @@ class LatticeSource:
         self.gq_all = sorted({r[0] for _, row in prows for r in row[2]} | {d for d, row in prows if len(row) > 3})
         # the components with Jacobian entries at the cell itself (the G accumulators)
         self.g_own = sorted({r[0] for _, row in prows for r in row[2] if len(r) < 4 or r[3] == 0})
+        self.zc, self.h = bool(self.zero_centered), bool(self.half)
+        for on, what in ((self.zc, 'zero_centered pdfs'), (self.h, 'float16 pdfs')):
+            if on and (self.rho_links or self.gen):
+                raise NotImplementedError(density_links_message(what))
+        if self.h and (self.ff or self.of):
+            raise NotImplementedError('lattice kernels for float16 pdfs: a per-cell force / relaxation-rate field is '
+                                      'not built (its adjoint would accumulate in float16)')
 
 
 class _Addressing:
@@ -126,8 +154,9 @@ class _Addressing:
     def __init__(self, spec):
         self.buf = spec.hip and spec.addr == 'buf'
         self.ct, self.axes, self.keys = spec.ctype, spec.axes, spec.keys
-        self.esize = 8 if spec.ctype == 'double' else 4
-        self.bits, self.ty = ('b64', 'u32x2') if self.esize == 8 else ('b32', 'unsigned')
+        self.esize = 2 if spec.h else 8 if spec.ctype == 'double' else 4
+        self.bits, self.ty = {8: ('b64', 'u32x2'), 4: ('b32', 'unsigned'), 2: ('b16', 'unsigned short')}[self.esize]
+        self.half, self.chalf = spec.h, spec.h and not spec.hip       # (C: uint16_t bits and conversion helpers)
         self.off_type = 'unsigned' if self.buf else 'IDX'      # of a cell's (byte / element) offset
 
     def coord(self, k, a):
@@ -157,16 +186,37 @@ class _Addressing:
             L.append(f'  const unsigned {p}cb = (unsigned){p}c * {self.esize}u;')
         return f'{p}cb' if self.buf else f'{p}c'
 
+    def _rd(self, e):
+        """The element ``e`` of a pdf array as a value (half floats: converted to the compute type)."""
+        return f'({self.ct})psad_h2f({e})' if self.chalf else f'({self.ct}){e}' if self.half else e
+
+    def _wr(self, val, paren=True):
+        """``val`` in the storage type (half floats on the C target: rounded to nearest-even by the helper)."""
+        if self.chalf:
+            return f'psad_f2h((float)({val}))'
+        return f'(T)({val})' if paren else f'(T){val}'
+
     def load(self, p, comp, off):
         """Component ``comp`` (a constant: its plane offset is a scalar) at cell offset ``off``."""
         if self.buf:
             return self._buffer_load(p, off, f'{comp} * {p}_qb')
-        return f'({self.ct}){ARRAYS[p]}[(IDX){comp} * {p}_q + {off}]'
+        # (always cast, as this load always was; ``_rd`` casts half floats only: the loads that go through it alone —
+        # ``load_v``, ``select_load`` — had no cast, and the plain sources stay what they were, to the byte)
+        e = f'{ARRAYS[p]}[(IDX){comp} * {p}_q + {off}]'
+        return self._rd(e) if self.chalf else f'({self.ct}){e}'
+
+    def copy(self, p, comp, off, sp, soff):
+        """``p[comp, off] = sp[comp, soff]`` as the stored bits, never converted (half floats: an obstacle cell's
+        copy keeps NaN payloads too)."""
+        if self.buf:
+            return (f'__builtin_amdgcn_raw_buffer_store_{self.bits}(__builtin_amdgcn_raw_buffer_load_{self.bits}('
+                    f'rs_{sp}, {soff}, {comp} * {sp}_qb, 0), rs_{p}, {off}, {comp} * {p}_qb, 0);')
+        return f'{ARRAYS[p]}[(IDX){comp} * {p}_q + {off}] = {ARRAYS[sp]}[(IDX){comp} * {sp}_q + {soff}];'
 
     def store(self, p, comp, off, val):
         if self.buf:
             return self._buffer_store(p, off, f'{comp} * {p}_qb', val)
-        return f'{ARRAYS[p]}[(IDX){comp} * {p}_q + {off}] = (T)({val});'
+        return f'{ARRAYS[p]}[(IDX){comp} * {p}_q + {off}] = {self._wr(val)};'
 
     def lane(self, p, comp, k):
         """The per-lane offset of (component, neighbour cell ``k``): the plane offset folded in."""
@@ -174,20 +224,22 @@ class _Addressing:
 
     def load_v(self, p, voff):
         """One load at a per-lane offset (``lane``; no scalar offset)."""
-        return self._buffer_load(p, voff, '0') if self.buf else f'{ARRAYS[p]}[{voff}]'
+        return self._buffer_load(p, voff, '0') if self.buf else self._rd(f'{ARRAYS[p]}[{voff}]')
 
     def store_v(self, p, voff, val):
         """One store of the variable ``val`` at a per-lane offset."""
-        return self._buffer_store(p, voff, '0', val) if self.buf else f'{ARRAYS[p]}[{voff}] = (T){val};'
+        return self._buffer_store(p, voff, '0', val) if self.buf else \
+            f'{ARRAYS[p]}[{voff}] = {self._wr(val, paren=False)};'
 
-    def select_load(self, L, decl, p, bit, bounced, pulled):
+    def select_load(self, L, decl, p, bit, bounced, pulled, shift=''):
         """``decl = msk bit ? array[bounced] : array[pulled]`` (lane offsets) as ONE load whose per-lane offset
-        selects (component, cell) — not both loads and a select."""
+        selects (component, cell) — not both loads and a select. ``shift``: the `` + w`` of zero-centred pdfs."""
         if self.buf:
             L.append(f'  const unsigned vo{bit} = ((msk >> {bit}) & 1u) ? {bounced} : {pulled};')
-            L.append(f'  {decl} = {self.load_v(p, f"vo{bit}")};')
+            L.append(f'  {decl} = {self.load_v(p, f"vo{bit}")}{shift};')
         else:
-            L.append(f'  {decl} = {ARRAYS[p]}[(msk >> {bit}) & 1u ? {bounced} : {pulled}];')
+            L.append(f'  {decl} = ' + self._rd(f'{ARRAYS[p]}[(msk >> {bit}) & 1u ? {bounced} : {pulled}]') +
+                     f'{shift};')
 
     def select_store(self, L, p, bit, bounced, pulled, val):
         """The store likewise (closes the block of the component)."""
@@ -195,7 +247,8 @@ class _Addressing:
             L.append(f'    const unsigned vs = ((msk >> {bit}) & 1u) ? {bounced} : {pulled};')
             L.append(f'    {self.store_v(p, "vs", val)} }}')
         else:
-            L.append(f'    {ARRAYS[p]}[(msk >> {bit}) & 1u ? {bounced} : {pulled}] = (T){val}; }}')
+            L.append(f'    {ARRAYS[p]}[(msk >> {bit}) & 1u ? {bounced} : {pulled}] = '
+                     f'{self._wr(val, paren=False)}; }}')
 
     def atomic_add(self, voff, val):
         """``out[voff] += val`` atomically (``voff``: a lane offset)."""
@@ -292,7 +345,11 @@ class _Printer:
         s, L = self.s, []
         if not s.hip:
             L.append('#include <stdint.h>\ntypedef long long i64;')
-        L.append(f'typedef {s.ctype} T;\ntypedef {s.idx} IDX;')
+        if s.h and not s.hip:
+            # the pdf arrays hold the half floats' bits: the CPU backend's conversion helpers
+            from ..backends.cpu_kernel import _HALF_HELPERS
+            L.append('#include <string.h>' + _HALF_HELPERS.rstrip('\n'))
+        L.append(f'typedef {("_Float16" if s.hip else "uint16_t") if s.h else s.ctype} T;\ntypedef {s.idx} IDX;')
         if s.hip:
             L.append('typedef unsigned u32x2 __attribute__((ext_vector_type(2)));')
         self.link_tables(L)
@@ -332,6 +389,10 @@ class _Printer:
         incompressible one w_i (ρ + …)."""
         return (f'{self.c_(self.w[i])} * rho * (({self.ct})1 + poly)' if self.s.compressible
                 else f'{self.c_(self.w[i])} * (rho + poly)')
+
+    def shift(self, i, sign=' + '):
+        """Zero-centred pdfs: `` + w_i`` after a load of a state value, `` - w_i`` before a forward result's store."""
+        return f'{sign}{self.c_(self.w[i])}' if self.s.zc else ''
 
     def mat_row(self, M, vec, i, transpose=False):
         """Σ_k M[i][k] vec_k (or M[k][i]) as C, zero entries left out (None when the row is all zeros)."""
@@ -390,7 +451,8 @@ class _Printer:
         s, Q = self.s, self.Q
         if s.links is None:
             return
-        qual = '__constant__ T' if s.hip else 'static const T'
+        # (half pdfs: the coefficients stay in the compute type)
+        qual = ('__constant__ ' if s.hip else 'static const ') + (self.ct if s.h else 'T')
         cols = (('lk_a', 0), ('lk_b', 1), ('lk_g', 2)) + ((('lk_r', 3), ('lk_gr', 4)) if s.rho_links else ())
         for nm, col in cols:
             vals = [repr(float(s.links[k][self.inv[j]][col] if col < len(s.links[k][self.inv[j]]) else 0.0))
@@ -427,7 +489,7 @@ class _Printer:
         for i in range(Q):
             k = _key(self.dirs[i])
             if not (s.walls and any(self.dirs[i])):
-                L.append(f'  const {ct} f{i} = {A.load("s", i, f"so_{k}")};')
+                L.append(f'  const {ct} f{i} = {A.load("s", i, f"so_{k}")}{self.shift(i)};')
                 continue
             cq = '' if s.links is not None else 'const '
             bounced, pulled = A.lane('s', self.inv[i], centre), A.lane('s', i, k)
@@ -437,7 +499,7 @@ class _Printer:
                 L.append(f'  {cq}{ct} f{i} = ((msk >> {i}) & 1u) ? fb{i} : fs{i};')
             else:
                 # a bounced component is read from the cell itself
-                A.select_load(L, f'{cq}{ct} f{i}', 's', i, bounced, pulled)
+                A.select_load(L, f'{cq}{ct} f{i}', 's', i, bounced, pulled, self.shift(i))
             if s.links is None:
                 continue
             # the wall cell's link (moving wall: α = 1, β = 6 w (c·u)); its id is loaded on this path only
@@ -500,12 +562,14 @@ class _Printer:
             L.append(f'  const {ct} w_odd = {wo};')
             L.append(f'  const {ct} ta = ({ct})0.5 * (omega + w_odd), tb = ({ct})0.5 * (omega - w_odd);')
 
-    def obstacle_copy(self, L, p, off, val):
-        """An obstacle cell keeps its state (forward: ``dst = src``; adjoint: ``out = g``)."""
+    def obstacle_copy(self, L, p, off, sp, soff):
+        """An obstacle cell keeps its state (forward: ``dst = src``; adjoint: ``out = g``): array ``sp`` at ``soff`` to
+        array ``p`` at ``off`` (half floats: the bits themselves, no conversion on the way)."""
+        A = self.A
         L.append(f'  const unsigned msk = nbmask[{self.cell}];')
         L.append(f'  if ((msk >> {SELF_BIT}) & 1u) {{')
         for i in range(self.Q):
-            L.append('    ' + self.A.store(p, i, off, val(i)))
+            L.append('    ' + (A.copy(p, i, off, sp, soff) if self.s.h else A.store(p, i, off, A.load(sp, i, soff))))
         L.append('    return;\n  }')
 
     # ---- forward
@@ -525,7 +589,7 @@ class _Printer:
         A.neighbour_offsets(L, 's')
         dcoff = A.cell_offset(L, 'd')
         if s.walls:
-            self.obstacle_copy(L, 'd', dcoff, lambda i: A.load('s', i, f'so_{self.centre}'))
+            self.obstacle_copy(L, 'd', dcoff, 's', f'so_{self.centre}')
 
         self.force_loads(L)
         self.omega_load(L)
@@ -557,7 +621,7 @@ class _Printer:
                 val = f'f{i}' + (f' - omega * ({pw})' if pw else '') + (f' - ({cc})' if cc else '') + term
             else:
                 val = f'f{i} + omega * ({self.feq(i)} - f{i}){term}'
-            L.append('    ' + A.store('d', i, dcoff, val) + ' }')
+            L.append('    ' + A.store('d', i, dcoff, val + self.shift(i, ' - ')) + ' }')
         L.append('}')
 
     # ---- adjoint (scatter to where the forward pulled from)
@@ -627,7 +691,7 @@ class _Printer:
         onto zero, the same sum in either order, so the result is the one a second fix-up launch (``out += G`` after
         every other store) would give."""
         s, A = self.s, self.A
-        self.obstacle_copy(L, 'o', f'oo_{self.centre}', lambda i: A.load('g', i, gcoff))
+        self.obstacle_copy(L, 'o', f'oo_{self.centre}', 'g', gcoff)
         if s.mode != 'main':
             return
         # a cell next to a program wall is the fix-up kernel's: it only zeroes the entries out_q(x), q in gq, that

@@ -26,7 +26,8 @@ import sympy as sp
 from .. import ps
 
 __all__ = ['LBStencil', 'create_lb_update_rule', 'create_lb_adjoint_rule', 'macroscopic_getter',
-           'equilibrium_setter', 'relaxation_rate_from_magic_number', 'mrt_moments', 'mrt_relaxation_matrices']
+           'equilibrium_setter', 'macroscopic_setter', 'relaxation_rate_from_magic_number', 'mrt_moments',
+           'mrt_relaxation_matrices']
 
 
 class LBStencil:
@@ -136,6 +137,12 @@ def _feq(stencil, i, rho, us, compressible):
     return w * rho * (1 + poly) if compressible else w * (rho + poly)
 
 
+def _pulled(stencil, src_field, zero_centered):
+    """The pulled pdfs ``f_i = src_i(x − c_i)`` of a cell (zero-centred storage: ``+ w_i``)."""
+    return [src_field[tuple(-c for c in stencil.directions[i])](i) + (stencil.weights[i] if zero_centered else 0)
+            for i in range(stencil.Q)]
+
+
 def relaxation_rate_from_magic_number(relaxation_rate, magic_number=sp.Rational(3, 16)):
     """The odd-moment rate of a TRT method from the even one and the magic number
     Λ = (1/ω₊ − 1/2)(1/ω₋ − 1/2) (lbmpy ``relaxation_rate_from_magic_number`` [ext], default Λ = 3/16)."""
@@ -214,7 +221,8 @@ def mrt_relaxation_matrices(stencil):
 
 def create_lb_update_rule(stencil='D2Q9', relaxation_rate=None, compressible=False, src_field=None, dst_field=None,
                           data_type='float64', layout='fzyx', kernel_type='stream_pull_collide', force_model=None,
-                          force=None, method='srt', relaxation_rates=None, magic_number=sp.Rational(3, 16)):
+                          force=None, method='srt', relaxation_rates=None, magic_number=sp.Rational(3, 16),
+                          zero_centered=False):
     """SRT (BGK) or TRT ``stream_pull_collide`` update rule (lbmpy ``create_lb_update_rule(stencil=…,
     method='srt' | 'trt', relaxation_rate=…, compressible=…, kernel_type='stream_pull_collide')`` [ext]).
     ``relaxation_rate`` = ω: a number, or a sympy symbol left as a kernel parameter (default: the symbol ``omega``).
@@ -237,7 +245,12 @@ def create_lb_update_rule(stencil='D2Q9', relaxation_rate=None, compressible=Fal
     Fields: ``src(q)``/``dst(q)`` vector fields in ``layout`` (``'fzyx'``: components slowest, lbmpy's default)
     unless given. ``force_model`` ('simple' or 'guo', with every method: Guo's force term is scaled by 1 − ω/2 with
     the shear rate ω) with ``force``: a body force — constant (numbers or symbols per axis) or per cell (a vector
-    field of D components: an additional input of the rule, its adjoint accumulated over the steps)."""
+    field of D components: an additional input of the rule, its adjoint accumulated over the steps).
+
+    ``zero_centered``: the pdf fields hold ``δf_i = f_i − w_i`` (lbmpy's zero-centred storage [ext], background
+    density 1) — the pulled values are ``f_i = src_i(x − c_i) + w_i`` and the rule assigns ``dst_i ← (collision + force
+    term)_i − w_i``: the stored numbers are of the size of the flow's signal, not of the weights, which is what makes
+    ``data_type='float16'`` pdfs usable (``ac.zero_centered``; the macroscopic getter / setter take the same flag)."""
     if kernel_type != 'stream_pull_collide':
         raise NotImplementedError("only kernel_type='stream_pull_collide' is restated")
     method = str(method).lower()
@@ -256,7 +269,7 @@ def create_lb_update_rule(stencil='D2Q9', relaxation_rate=None, compressible=Fal
             raise ValueError('relaxation_rates: for the TRT / MRT methods (SRT: relaxation_rate)')
         relaxation_rate = relaxation_rates[0]
     omega = sp.Symbol('omega') if relaxation_rate is None else sp.sympify(relaxation_rate)
-    f = [src_field[tuple(-c for c in st.directions[i])](i) for i in range(st.Q)]
+    f = _pulled(st, src_field, zero_centered)
     # Guo with TRT / MRT: lbmpy's Guo model scales the force term by 1 − ω/2 with the shear rate ω [ext] (not by
     # moment group); the velocity shift F/2 as for SRT
     shift, term = _force(force_model, force, st)
@@ -280,9 +293,12 @@ def create_lb_update_rule(stencil='D2Q9', relaxation_rate=None, compressible=Fal
         inv = [st.inverse_direction_index(i) for i in range(st.Q)]
         coll = [f[i] - omega * ((f[i] + f[inv[i]]) / 2 - (feq[i] + feq[inv[i]]) / 2)
                 - omega_odd * ((f[i] - f[inv[i]]) / 2 - (feq[i] - feq[inv[i]]) / 2) for i in range(st.Q)]
-    main = [ps.Assignment(dst_field.center(i), coll[i] + (term(i, us, omega) if term else 0)) for i in range(st.Q)]
+    back = [st.weights[i] if zero_centered else 0 for i in range(st.Q)]
+    main = [ps.Assignment(dst_field.center(i), coll[i] + (term(i, us, omega) if term else 0) - back[i])
+            for i in range(st.Q)]
     ac = ps.AssignmentCollection(main, subs)
     ac.stencil = st
+    ac.zero_centered = bool(zero_centered)
     ac.compressible = compressible
     ac.relaxation_rate = omega
     ac.method = method
@@ -317,7 +333,8 @@ def create_lb_adjoint_rule(update_rule, diff_fields_prefix='diff'):
     (src,), (dst,) = tuple(src), tuple(dst)
     from .._adjoint_field import AdjointField
     dsrc, ddst = AdjointField(src, diff_fields_prefix), AdjointField(dst, diff_fields_prefix)
-    f = [src[tuple(-c for c in st.directions[i])](i) for i in range(st.Q)]
+    # (zero-centred pdfs: the shift is a constant, so the Jacobian is the same function — evaluated at src + w)
+    f = _pulled(st, src, getattr(update_rule, 'zero_centered', False))
     g = [ddst.center(i) for i in range(st.Q)]
     rho, us, subs = _moments(st, f, comp)
     feq = [_feq(st, i, rho, us, comp) for i in range(st.Q)]
@@ -361,11 +378,12 @@ def create_lb_adjoint_rule(update_rule, diff_fields_prefix='diff'):
 
 
 def macroscopic_getter(stencil, pdf_field, density_field, velocity_field, compressible=False, force_model=None,
-                       force=None):
+                       force=None, zero_centered=False):
     """ρ = Σ f_i, u = Σ c_i f_i (/ρ): lbmpy's ``macroscopic_values_getter`` [ext] for the SRT method (Guo's
-    forcing: the velocity shifted by F/2)."""
+    forcing: the velocity shifted by F/2). ``zero_centered`` pdfs ``δf = f − w``: ρ = 1 + Σ δf_i; the momentum is
+    unchanged (Σ c_i w_i = 0)."""
     st = stencil if isinstance(stencil, LBStencil) else LBStencil(stencil)
-    f = [pdf_field.center(i) for i in range(st.Q)]
+    f = [pdf_field.center(i) + (st.weights[i] if zero_centered else 0) for i in range(st.Q)]
     shift, _ = _force(force_model, force, st)
     rho, us, subs = _moments(st, f, compressible, shift)
     main = [ps.Assignment(density_field.center, rho)] + \
@@ -373,13 +391,17 @@ def macroscopic_getter(stencil, pdf_field, density_field, velocity_field, compre
     return ps.AssignmentCollection(main, subs)
 
 
-def equilibrium_setter(stencil, pdf_field, density_field, velocity_field, compressible=False):
-    """pdfs = feq(ρ, u): lbmpy's ``macroscopic_values_setter`` [ext] (equilibrium initialisation)."""
+def equilibrium_setter(stencil, pdf_field, density_field, velocity_field, compressible=False, zero_centered=False):
+    """pdfs = feq(ρ, u): lbmpy's ``macroscopic_values_setter`` [ext] (equilibrium initialisation); ``zero_centered``
+    pdfs get ``feq − w``."""
     st = stencil if isinstance(stencil, LBStencil) else LBStencil(stencil)
     rho = density_field.center
     us = [velocity_field.center(a) for a in range(st.D)]
-    return ps.AssignmentCollection([ps.Assignment(pdf_field.center(i), _feq(st, i, rho, us, compressible))
-                                    for i in range(st.Q)], [])
+    return ps.AssignmentCollection([ps.Assignment(pdf_field.center(i), _feq(st, i, rho, us, compressible) -
+                                                  (st.weights[i] if zero_centered else 0)) for i in range(st.Q)], [])
+
+
+macroscopic_setter = equilibrium_setter
 
 
 def _check_directions():

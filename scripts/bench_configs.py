@@ -236,7 +236,7 @@ def run_slab(name, builder, shape, dtype, full_cells, steps=20, warmup=3):
 
 
 def run_lbm(name, stencil, shape, dtype, T=10, reps=5, compressible=False, walls=False, force_model=None,
-            force_field=False, method='srt', omega_field=False):
+            force_field=False, method='srt', omega_field=False, zero_centered=False):
     """Lattice Boltzmann time-step op (lbm.AutoDiffLatticeBoltzmannStep.create_timestep_op): T forward steps
     and the T adjoint steps, HIP events around Op.apply and backward (back-to-back applies). MLUPS = cells · T / time; algorithmic
     bytes per cell and step: forward 2q·s (read src, write dst), adjoint 3q·s (read diffdst and the recorded
@@ -244,7 +244,8 @@ def run_lbm(name, stencil, shape, dtype, T=10, reps=5, compressible=False, walls
     ``force_field``: a per-cell force (a D-component fzyx field, an input of the op): + D·s per cell and step forward
     (the force read), + 3·D·s adjoint (the force read, its accumulated adjoint read and written).
     ``omega_field``: the relaxation rate per cell (a scalar field, an input of the op): + s forward (the ω read), + 3·s
-    adjoint (the ω read, its accumulated adjoint read and written) — (2q + 1)·s and (3q + 3)·s."""
+    adjoint (the ω read, its accumulated adjoint read and written) — (2q + 1)·s and (3q + 3)·s.
+    ``zero_centered``: the pdf arrays hold f − w (the float16 rows; s = 2 there)."""
     import sympy as sp
     import torch
 
@@ -259,7 +260,7 @@ def run_lbm(name, stencil, shape, dtype, T=10, reps=5, compressible=False, walls
     if omega_field:
         mk['relaxation_rate'] = ps.fields(f"omega_f: {dts}[{D}D]").center
     rule = lbm.create_lb_update_rule(stencil, compressible=compressible, data_type=dts, force_model=force_model,
-                                     force=force, **mk)
+                                     force=force, zero_centered=zero_centered, **mk)
     step = lbm.AutoDiffLatticeBoltzmannStep(rule, domain_size=shape, relaxation_rate=None if omega_field else 1.5,
                                             target='gpu')
     if walls == 'freeslip':
@@ -279,7 +280,10 @@ def run_lbm(name, stencil, shape, dtype, T=10, reps=5, compressible=False, walls
     q = rule.stencil.Q
     g = torch.Generator(device='cuda').manual_seed(0)
     f0 = (torch.full(tuple(shape) + (q,), 1.0 / q, device='cuda', dtype=torch.float64) *
-          (1 + 0.01 * torch.rand(tuple(shape) + (q,), generator=g, device='cuda', dtype=torch.float64))).to(dtype)
+          (1 + 0.01 * torch.rand(tuple(shape) + (q,), generator=g, device='cuda', dtype=torch.float64)))
+    if zero_centered:
+        f0 = f0 - torch.tensor([float(w) for w in rule.stencil.weights], device='cuda', dtype=torch.float64)
+    f0 = f0.to(dtype)
     # inputs in the step's fzyx layout (one plane per component): no layout copies inside the op
     x = step.empty_pdfs()
     x.copy_(f0)
@@ -338,6 +342,8 @@ def run_lbm(name, stencil, shape, dtype, T=10, reps=5, compressible=False, walls
                              / (b_ms * 1e-3) / 1e9, 1),
            'force': (f'{force_model}, per-cell field' if force_field else force_model) if force_model else None,
            'method': method}
+    if zero_centered:
+        res['zero_centered'] = True
     if omega_field:
         res['omega'] = 'per-cell field'
     res['fwd_frac'] = round(res['fwd_GBps'] / PEAK, 4)
@@ -442,13 +448,19 @@ def main():
             ('lbm_d3q19_f32_192^3_mrt', 'D3Q19', (192, 192, 192), torch.float32, False, 'mrt'),
             # ω read per cell from a scalar field, its adjoint accumulated (next to their scalar-ω twins above)
             ('lbm_d2q9_f32_2048^2_omega_field', 'D2Q9', (2048, 2048), torch.float32, False, 'srt', True),
-            ('lbm_d3q19_f32_192^3_omega_field', 'D3Q19', (192, 192, 192), torch.float32, False, 'srt', True)]
+            ('lbm_d3q19_f32_192^3_omega_field', 'D3Q19', (192, 192, 192), torch.float32, False, 'srt', True),
+            # float16 pdfs, zero-centred (2 bytes per pdf; PSAD_LBM_LATTICE=0 runs the periodic ones on the rule's
+            # AutoDiffOp kernels, which have no walls)
+            ('lbm_d2q9_f16_2048^2', 'D2Q9', (2048, 2048), torch.float16, False, 'srt', False, True),
+            ('lbm_d3q19_f16_192^3', 'D3Q19', (192, 192, 192), torch.float16, False, 'srt', False, True),
+            ('lbm_d2q9_f16_2048^2_channel', 'D2Q9', (2048, 2048), torch.float16, True, 'srt', False, True),
+            ('lbm_d3q19_f16_192^3_channel', 'D3Q19', (192, 192, 192), torch.float16, True, 'srt', False, True)]
     for name, stencil, shape, dt, walls, *more in lbms:
         if only and name not in only:
             continue
         for _ in range(repeat):
             run_lbm(name, stencil, shape, dt, walls=walls, method=more[0] if more else 'srt',
-                    omega_field=len(more) > 1 and more[1])
+                    omega_field=len(more) > 1 and more[1], zero_centered=len(more) > 2 and more[2])
 
 
 if __name__ == '__main__':
