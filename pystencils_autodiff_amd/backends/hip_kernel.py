@@ -310,8 +310,8 @@ class HipStencilKernel:
         fns = self.function(('pointwise',), device)
         n = int(np.prod(shape))
         aligned = all(t.data_ptr() % 32 == 0 for t in tensors)
-        per_block = 256 * (4 * he.POINTWISE_UNROLL if aligned else 1)
-        cap = (he.POINTWISE_MAX_BLOCKS or 2 ** 31 - 1) if aligned else 256 * 16
+        per_block = 256 * (4 * he.pointwise.POINTWISE_UNROLL if aligned else 1)
+        cap = (he.pointwise.POINTWISE_MAX_BLOCKS or 2 ** 31 - 1) if aligned else 256 * 16
         blocks = max(1, min(math.ceil(n / per_block), cap))
         kinds = ['ptr'] * len(tensors) + ['i64'] + [self._scalar_kind()] * len(self.ir.scalars)
         return _Plan(('pointwise', 'v4' if aligned else 'v1'), fns['v4' if aligned else 'v1'], blocks, kinds,

@@ -20,7 +20,7 @@ reference's generated kernels have, independent of how they are scheduled:
 ``StencilKernel`` keeps pystencils' ``KernelFunction`` surface the reference
 touches (``function_name``, ``fields_accessed``, ``fields_read``,
 ``fields_written``, ``get_parameters()``, ``compile()``) and picks the
-schedule the HIP emitter prints (``hip_emitter.py``).
+schedule the HIP emitter prints (the ``hip_emitter`` package).
 """
 import hashlib
 import itertools

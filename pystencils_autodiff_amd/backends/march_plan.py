@@ -67,7 +67,7 @@ BAND_REG_STAR_ODD = 1
 BAND_F32_IDLE_MAX_X = 1024
 
 # (CX, NR) candidates of the LDS-DMA plane ring for stencils that are not linear off the centre plane
-# (hip_emitter._ring_ws_geometry), widest first: the first whose ring fits the LDS
+# (hip_emitter.geometry._ring_ws_geometry), widest first: the first whose ring fits the LDS
 RING_WS_TILES = ((4, 4), (4, 2), (2, 4), (2, 2), (1, 4), (1, 2), (1, 1))
 
 # gpu_indexing_params keys of pystencils' own GPU indexing (``block_size``, ``maximum_block_size``, …, e.g.
@@ -577,7 +577,7 @@ def _route(ir, plan, shape, stencil_align, all_align, restricted):
 def periodic_march_config(ir, ve, shape=None, tuning=None):
     """The tile of a periodic kernel (3-D, scalar fields): the stencil-class default without the row band, where it
     ends on an LDS-DMA loader (``ws_geometry``: the wrapped plane loads are the loader's,
-    ``hip_emitter._ws_piece_offsets``) — else, unless the overrides set ``WS`` themselves, the same tile with the loader on
+    ``hip_emitter.loader._ws_piece_offsets``) — else, unless the overrides set ``WS`` themselves, the same tile with the loader on
     (fp32 / fp64 box stencils, whose 'zeros' default is the register-prefetch form), and for fp16 storage last with
     ``CX=4`` as well: the half-precision rings' lanes own quads / pairs of x-adjacent cells, which rows narrower than
     the tile (or a ``CX`` override) would drop; a tile wider than the rows only loads wrapped duplicates — or None."""

@@ -116,8 +116,8 @@ def main():
         u, out = u.reshape(shape[0], shape[1], -1), out.reshape(shape[0], shape[1], -1)
     alg = 2 * esize * cells
     for nt_load, maxb in ((False, 2048), (True, 2048), (False, 0), (True, 0)):
-        _he.POINTWISE_NT_LOAD = nt_load
-        _he.POINTWISE_MAX_BLOCKS = maxb
+        _he.pointwise.POINTWISE_NT_LOAD = nt_load
+        _he.pointwise.POINTWISE_MAX_BLOCKS = maxb
         ck = StencilKernel(_ps.AssignmentCollection({co.center: cu.center}),
                            function_name=f'tunecopy{int(nt_load)}{maxb}', target='gpu').compile()
         ck(cu=u, co=out)
@@ -134,8 +134,8 @@ def main():
         pmed = sorted(pt)[len(pt) // 2]
         print(f"pointwise copy{' (nt loads)' if nt_load else ''}{' one pass' if not maxb else ''}: median {pmed:.4f} ms = "
               f"{alg / (pmed * 1e-3) / 1e9:.0f} GB/s")
-    _he.POINTWISE_NT_LOAD = True
-    _he.POINTWISE_MAX_BLOCKS = 0
+    _he.pointwise.POINTWISE_NT_LOAD = True
+    _he.pointwise.POINTWISE_MAX_BLOCKS = 0
     # torch's own vectorised elementwise kernel (read + write of the same bytes) for reference
     mt = []
     for _ in range(a.rounds):

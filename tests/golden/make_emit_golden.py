@@ -13,8 +13,9 @@ No GPU and no compile: the sources are text. ``tests/test_emit_golden.py`` compa
 
 A source that raises is recorded as ``ERROR <type>: <message>``.
 
-``python scripts/emit_coverage.py`` runs ``rows()`` under a line collector: every statement of the emitter files is
-executed except ``raise`` statements. When these rows were first generated, before any line of the emitter changed,
+``python scripts/emit_coverage.py`` runs ``rows()`` and the periodic rows of ``tests/test_periodic_march.py`` under a
+line collector: every statement of the emitter files (the ``hip_emitter`` package, ``hip_band.py``) is executed except
+``raise`` statements. When these rows were first generated, before any line of the emitter changed,
 the collector also left six statements in four places that no ``MarchConfig`` enters; they are deleted (every hash
 unchanged):
 
@@ -195,11 +196,11 @@ def _band_plan_rows():
 
 def pointwise_plain_loads(ir):
     """``emit_pointwise`` with the module switch ``POINTWISE_NT_LOAD`` off (``scripts/tune_march.py`` sets it)."""
-    saved, E.POINTWISE_NT_LOAD = E.POINTWISE_NT_LOAD, False
+    saved, E.pointwise.POINTWISE_NT_LOAD = E.pointwise.POINTWISE_NT_LOAD, False
     try:
         return E.emit_pointwise(ir, 'axpy')
     finally:
-        E.POINTWISE_NT_LOAD = saved
+        E.pointwise.POINTWISE_NT_LOAD = saved
 
 
 def explicit_rows():

@@ -1,5 +1,5 @@
 """``boundary_handling='periodic'`` on the march schedules: the LDS-DMA loader fills the plane image from wrapped
-source offsets (``hip_emitter._ws_piece_offsets``), out-of-domain planes are the kernel's own far planes or the z-slab
+source offsets (``hip_emitter.loader._ws_piece_offsets``), out-of-domain planes are the kernel's own far planes or the z-slab
 halos (``ws_plane_base``).
 
 CPU part: which kernels ``schedule()`` sends to ``'march'``, which launches the planner gives an LDS-DMA loader
