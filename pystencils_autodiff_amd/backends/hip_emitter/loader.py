@@ -65,7 +65,7 @@ def _ws_piece_offsets(f, g, NI, VE, esize, xo=False, periodic=False):
 # The compute waves' plane barrier over an LDS-DMA ring: every LDS read of the previous plane completes (lgkmcnt) before
 # the barrier and none moves past it (memory clobber). Once the loader passes this barrier it refills the slot read one
 # plane earlier, and its DMA writes are invisible to the compiler: with __syncthreads() hipcc 7.2 sank reads below the
-# next barrier in the band kernel (hip_band.py, scripts/probes/band_determinism.py). Audited in the ISA of every WS
+# next barrier in the band kernel (hip_band/steps.py, scripts/probes/band_determinism.py). Audited in the ISA of every WS
 # schedule (scripts/probes/barrier_audit.py: no ds_read outstanding at any s_barrier).
 WS_CONSUMER_BARRIER = 'asm volatile("s_waitcnt lgkmcnt(0)\\n\\ts_barrier" ::: "memory");'
 

@@ -1,5 +1,5 @@
 """``python scripts/emit_coverage.py``: the statements of the stencil emitter (every ``.py`` file of
-``backends/hip_emitter`` — the package, or the one module — and ``backends/hip_band.py``) that neither pinned generator
+``backends/hip_emitter`` and ``backends/hip_band`` — each the package, or the one module) that neither pinned generator
 executes, per function: ``rows()`` of ``tests/golden/make_emit_golden.py`` and ``periodic_rows()`` of
 ``tests/test_periodic_march.py`` run under a ``sys.settrace`` line collector (no coverage package needed). ``raise``
 statements are listed apart: the generators are complete when nothing else is left, and the exit status says so.
@@ -13,8 +13,9 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BACKENDS = os.path.join(ROOT, 'pystencils_autodiff_amd', 'backends')
-FILES = sorted(glob.glob(os.path.join(BACKENDS, 'hip_emitter.py')) +
-               glob.glob(os.path.join(BACKENDS, 'hip_emitter', '*.py'))) + [os.path.join(BACKENDS, 'hip_band.py')]
+FILES = [path for name in ('hip_emitter', 'hip_band')
+         for path in sorted(glob.glob(os.path.join(BACKENDS, name + '.py')) +
+                            glob.glob(os.path.join(BACKENDS, name, '*.py')))]
 
 
 def parse(path):

@@ -1,5 +1,5 @@
 """Generate ``tests/golden/emit_source_sha.json`` (run: python tests/golden/make_emit_golden.py): the SHA-256 of every
-HIP source the stencil emitter (``backends/hip_emitter``, ``backends/hip_band.py``) prints, over three sets of rows.
+HIP source the stencil emitter (``backends/hip_emitter``, ``backends/hip_band``) prints, over three sets of rows.
 No GPU and no compile: the sources are text. ``tests/test_emit_golden.py`` compares ``rows()`` with the JSON, so
 "no hash moved" means that a change of the emitter left every code object, and with it behaviour and speed, alone.
 
@@ -14,7 +14,7 @@ No GPU and no compile: the sources are text. ``tests/test_emit_golden.py`` compa
 A source that raises is recorded as ``ERROR <type>: <message>``.
 
 ``python scripts/emit_coverage.py`` runs ``rows()`` and the periodic rows of ``tests/test_periodic_march.py`` under a
-line collector: every statement of the emitter files (the ``hip_emitter`` package, ``hip_band.py``) is executed except
+line collector: every statement of the emitter files (the ``hip_emitter`` and ``hip_band`` packages) is executed except
 ``raise`` statements. When these rows were first generated, before any line of the emitter changed,
 the collector also left six statements in four places that no ``MarchConfig`` enters; they are deleted (every hash
 unchanged):

@@ -1,4 +1,4 @@
-"""Row-band schedule (``backends/hip_band.py``): fp16 stencils on full-width bands of rows.
+"""Row-band schedule (``backends/hip_band``): fp16 stencils on full-width bands of rows.
 
 CPU part: eligibility (one fp16 stencil field, linear taps, radius 1), the (band height, rows per lane, depth)
 choice and that the emitted kernels hiprtc-compile for gfx950. GPU part (``-m gpu``): forward and adjoint vs
@@ -62,6 +62,35 @@ def test_band_choice_and_geometry():
         g = band_geometry(X, TY, R, D)
         assert g['ntask'] % 64 == 0 and g['NCT'] <= 960 and D * g['NI'] <= 63
         assert g['lds_bytes'] <= (160 if (TY, R) == (16, 2) else 80) * 1024
+
+
+def test_band_tables_row_forms():
+    """The row form ``band_tables`` derives for the 27-point kernels (no GPU, no compile): rows of whole chunks, of a
+    partial last chunk and on half dwords. The expected values come from the row length and element size alone."""
+    from pystencils_autodiff_amd.backends.hip_band import band_tables
+    from pystencils_autodiff_amd.backends.hip_emitter import MarchConfig
+    for dtype, X in (('float16', 256), ('float16', 255), ('float16', 262), ('float16', 257), ('float32', 256),
+                     ('float32', 255)):
+        op = pa.AutoDiffOp(W.stencil_27pt(dtype=dtype), boundary_handling='zeros')
+        ir = HipStencilKernel(_kernel(op.forward_assignments)).ir
+        es = np.dtype(dtype).itemsize
+        VE = 16 // es
+        cfg = default_march_config(ir, VE, (32, 64, X), {'BAND': 4})
+        assert cfg.BAND == 4 and cfg.BX == X, cfg
+        if X % VE:                       # the launch plan masks the stores of a partial last chunk
+            cfg = MarchConfig(**{**cfg.__dict__, 'BMASK': True})
+        T = band_tables(ir, cfg)
+        assert (T.es, T.VE, T.X) == (es, VE, X)
+        # exclusive forms: a padded image, or row-wise pieces with zero fill (half-dword rows are a case of those)
+        assert not (T.padded and T.bu) and not (T.padded and T.bo), T
+        assert not T.bo or T.bu, T
+        assert T.bu == (not T.padded and (X * es) % 16 != 0), T
+        assert T.partial == (X % VE != 0), T
+        assert T.bo == ((X * es) % 4 != 0 and not cfg.BREG), T
+        assert T.tail_sb == ((VE - X % VE) % VE) * es, T
+        g = band_geometry(X, cfg.BTY, cfg.BAND, cfg.D, es, cfg.BPAD, cfg.BREG, cfg.BFREE)
+        assert T.XP == g['XP'] and T.g['lds_bytes'] == g['lds_bytes'], (T.XP, T.g, g)
+        assert T.XP % VE == 0 and T.XP >= X + (VE if T.padded else 0), T
 
 
 @pytest.mark.parametrize('shape,expect,zc', [((768, 768, 768), 2, 48), ((1024, 1024, 1024), 4, 32),

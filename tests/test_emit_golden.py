@@ -1,4 +1,4 @@
-"""The stencil emitter (``backends/hip_emitter``, ``backends/hip_band.py``) pinned on the CPU: every row of
+"""The stencil emitter (``backends/hip_emitter``, ``backends/hip_band``) pinned on the CPU: every row of
 ``tests/golden/make_emit_golden.py`` — the sources of every plan of the march-plan matrix and of the benchmark shapes,
 and direct calls of the emit functions for what no plan reaches — prints the text whose SHA-256
 ``tests/golden/emit_source_sha.json`` records (generated before any line of the emitter changed). A change that
