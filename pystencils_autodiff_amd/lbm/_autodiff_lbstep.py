@@ -200,7 +200,9 @@ class AutoDiffLatticeBoltzmannStep:
         from ._method import force_is_field
         if getattr(update_rule, 'stencil', None) is not None and not time_constant_fields and \
                 getattr(update_rule, 'force_model', None) in (None, 'simple') and \
-                not force_is_field(getattr(update_rule, 'force', None)) and not self._additional_fields:
+                not force_is_field(getattr(update_rule, 'force', None)) and not self._additional_fields and \
+                getattr(update_rule, 'smagorinsky', None) is None:
+            # (nor is the Smagorinsky model's rate, a function of the pdfs: the generic derivation as well)
             from ._method import create_lb_adjoint_rule
             backward = create_lb_adjoint_rule(update_rule)
         # the rule's AutoDiffOp (its kernels are the schedule for rules the lattice kernels do not take, and its
@@ -283,8 +285,14 @@ class AutoDiffLatticeBoltzmannStep:
                         tgt[i][k] += scale * float(P[grp][i][k])
             else:
                 self._lattice_mrt = (Pw, Cm)
+        # Smagorinsky: a numeric C_s is a constant of the lattice kernels; a symbolic one, float16 pdfs or a per-cell
+        # force field (its adjoint would need ∂ω_eff/∂F) run on the AutoDiffOp kernels
+        cs = getattr(update_rule, 'smagorinsky', None)
+        self._lattice_smagorinsky = float(cs) if cs is not None and sp.sympify(cs).is_number else None
+        smag_ok = cs is None or (self._lattice_smagorinsky is not None and self._force_field is None
+                                 and np.dtype(src.dtype.numpy_dtype) != np.float16)
         self._lattice = {} if (getattr(update_rule, 'stencil', None) is not None and not time_constant_fields
-                               and self._lattice_force is not None
+                               and self._lattice_force is not None and smag_ok
                                and os.environ.get('PSAD_LBM_LATTICE', '1') != '0'
                                and extras_ok and trt_ok and self._omega_of is not None
                                and np.dtype(src.dtype.numpy_dtype) in (np.float16, np.float32, np.float64)
@@ -305,6 +313,11 @@ class AutoDiffLatticeBoltzmannStep:
     def _autodiff(self):
         if self._autodiff_op is None:
             self._autodiff_op = AutoDiffOp(**self._autodiff_args)
+            fwd = getattr(self, '_forward_only', None)
+            if fwd is not None:
+                # the forward kernel that already ran (``_forward_kernel``) IS the op's: one compiled kernel, whose
+                # ``last_variant`` reports the launches made before the op existed
+                self._autodiff_op._kernels[('forward', fwd.target)] = fwd
         return self._autodiff_op
 
     def _adjoint_name(self, field):
@@ -517,14 +530,16 @@ class AutoDiffLatticeBoltzmannStep:
     def _lattice_kernels(self):
         walls = self._boundary.has_walls
         links, programs = self._link_data()
-        k = self._lattice.get((walls, links, programs))
+        key = (walls, links, programs, self._lattice_smagorinsky)
+        k = self._lattice.get(key)
         if k is None:
-            k = self._lattice[(walls, links, programs)] = LatticeKernels(
+            k = self._lattice[key] = LatticeKernels(
                 self.method, getattr(self._update_rule, 'compressible', False), self.pdf_field.dtype.numpy_dtype,
                 walls, self._target, links, *self._lattice_force, force_field=self._force_field is not None,
                 trt=self._lattice_trt, programs=programs, mrt=self._lattice_mrt,
                 omega_field=self._omega_field is not None,
-                zero_centered=getattr(self._update_rule, 'zero_centered', False))
+                zero_centered=getattr(self._update_rule, 'zero_centered', False),
+                smagorinsky=self._lattice_smagorinsky)
         return k
 
     # -- kernels -----------------------------------------------------------------------------------
@@ -539,8 +554,23 @@ class AutoDiffLatticeBoltzmannStep:
             return self._lattice_kernels().forward(src, dst, self._omega_of(), self._flag_arg(), ids=self._ids_arg(),
                                                    force=self._force_arg(extra), cells=self._cells_arg(),
                                                    omf=self._omega_arg(extra))
-        kf, _ = self._kernels()
+        kf = self._forward_kernel()
         kf(**{self._pdf_arr_name: src, self._tmp_arr_name: dst}, **extra, **self.kernel_params)
+
+    def _forward_kernel(self):
+        """The rule's forward kernel on the AutoDiffOp schedule. While the op does not exist yet — its transposed
+        derivation takes tens of seconds for a rule with square roots or a force field — a forward run compiles the
+        rule alone: the same assignments, boundary handling and kernel name as the op's forward kernel."""
+        if self._autodiff_op is not None:
+            return self._kernels()[0]
+        if getattr(self, '_forward_only', None) is None:
+            from ..autodiff import AutoDiffBoundaryHandling
+            from ..backends.kernel_ir import StencilKernel
+            tgt = 'gpu' if self._gpu else 'cpu'
+            self._forward_only = StencilKernel(self._update_rule,
+                                               boundary_handling=AutoDiffBoundaryHandling('periodic'),
+                                               function_name=f'LBM_forward_{tgt}', target=tgt)
+        return self._forward_only.compile()
 
     def _force_arg(self, extra):
         """The per-cell force array of the lattice kernels (None without a force field)."""

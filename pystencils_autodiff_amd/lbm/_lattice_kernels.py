@@ -114,8 +114,12 @@ class LatticeKernels:
     bounce-back)."""
 
     def __init__(self, stencil, compressible, dtype, walls, target, links=None, force_model=None, force=None,
-                 force_field=False, trt=None, programs=None, mrt=None, *, omega_field=False, zero_centered=False):
+                 force_field=False, trt=None, programs=None, mrt=None, *, omega_field=False, zero_centered=False,
+                 smagorinsky=None):
         self.stencil = stencil
+        # the Smagorinsky constant C_s (None: no subgrid model): a constant of the emitted source, so of every cache
+        # key made from it
+        self.smagorinsky = None if smagorinsky is None else float(smagorinsky)
         # the state arrays hold f_i − w_i (``LatticeSource.zero_centered``); the adjoint arrays are not shifted
         self.zero_centered = bool(zero_centered)
         # ω read per cell from a scalar field ``[*domain]``, its adjoint accumulated by the adjoint launches
@@ -139,7 +143,8 @@ class LatticeKernels:
         self.spec = spec = LatticeSource(
             stencil, self.compressible, self.ct, self.walls, self.links, programs, force_model, self.force,
             self.force_field, self.trt, self.mrt, target='hip' if target == 'gpu' else 'c',
-            omega_field=self.omega_field, zero_centered=self.zero_centered, half=self.dtype == np.float16)
+            omega_field=self.omega_field, zero_centered=self.zero_centered, half=self.dtype == np.float16,
+            smagorinsky=self.smagorinsky)
         # density-weighted links: the adjoint takes a second pass (lbm_adj_rho) over a per-cell scratch array
         self.rho_links = spec.rho_links
         # link programs (boundaries.link_program). C: inline, a Q-component scratch array per cell and the second

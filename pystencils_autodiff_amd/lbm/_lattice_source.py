@@ -79,6 +79,11 @@ class LatticeSource:
     the compute type only: with ``zero_centered`` or ``half`` they raise ``NotImplementedError`` (their second pass
     and fix-up launch accumulate in the storage type, and there is no single-half atomic), as do ``half`` force / ω
     fields (the field's adjoint would accumulate over the steps in half precision).
+    ``smagorinsky``: None, or the Smagorinsky constant C_s (``_method.create_lb_update_rule(smagorinsky=…)``): the rate
+    the collision reads is ``ω_eff = 2 / (τ0 + √(τ0² + 18 C_s² q))`` of the cell's own pulled pdfs, τ0 = 1/ω0 with ω0 the
+    ω argument or the ω field's value (``_Printer.smagorinsky_rate``), and the adjoint carries the chain factors
+    ``∂ω_eff/∂f_k`` on the scatter and ``∂ω_eff/∂ω0`` on ``domega`` (``_Printer.smagorinsky_adjoint``). Not printed
+    for ``half`` pdfs nor with a per-cell force field (whose adjoint would need ∂ω_eff/∂F): ``NotImplementedError``.
 
     The derived facts below follow from the fields in ``__post_init__``; a variant (another index type, addressing or
     mode) is made with ``dataclasses.replace``, never by assignment."""
@@ -100,6 +105,7 @@ class LatticeSource:
     omega_field: bool = False
     zero_centered: bool = False
     half: bool = False
+    smagorinsky: object = None
 
     def __post_init__(self):
         links, programs = self.links, self.programs
@@ -113,7 +119,18 @@ class LatticeSource:
         self.of = bool(self.omega_field)
         # Guo with TRT / MRT: the force term (prefactor 1 − ω/2 with the shear rate ω, as lbmpy's Guo model) is not
         # relaxed by the collision matrix, so its adjoint sums run over g while the equilibrium's run over h
-        self.gsplit = self.fm == 'guo' and (self.trt is not None or self.mrt is not None)
+        self.sm = None if self.smagorinsky is None else float(self.smagorinsky)
+        if self.sm is not None:
+            if not self.sm > 0:
+                raise ValueError(f'smagorinsky: a positive constant, got {self.smagorinsky!r}')
+            if self.half:
+                raise NotImplementedError('lattice kernels with smagorinsky: not built for float16 pdfs')
+            if self.ff:
+                raise NotImplementedError('lattice kernels with smagorinsky: not built with a per-cell force field '
+                                          '(its adjoint would need the derivative of the effective rate by the force)')
+        # (Smagorinsky: the equilibrium sums of every method run over h_i − λ P_i, ``smagorinsky_adjoint``, so SRT's
+        # force term is split off them as well)
+        self.gsplit = self.fm == 'guo' and (self.trt is not None or self.mrt is not None or self.sm is not None)
         # links whose value also depends on the fluid cell's density ρ(x) = Σ_k src_k(x) (a density-weighted moving
         # wall): forward f_j += βρ·ρ(x); the adjoint adds Σ_j βρ_j v_j to every component of the cell in a second pass
         self.rho_links = links is not None and any(len(t) > 3 and t[3] != 0 for lk in links for t in lk)
@@ -307,6 +324,10 @@ class _Printer:
         self.ncells = '(IDX)Z * Y * X'
         self.fn = '__device__ static inline' if s.hip else 'static inline'
         self.adj_progs = s.gen and s.mode != 'main'     # the main HIP adjoint leaves the program cells to the fix-up
+        # the rate: the scalar argument (unused with an ω field, which the cell loads), the cell's ω0 and — the name the
+        # collision reads — ``omega`` (Smagorinsky: the effective rate, computed from ω0 in ``moments``)
+        self.om0 = 'omega_0' if s.sm is not None else 'omega'
+        self.om_arg = 'omega_s' if s.of else self.om0
         self._signatures()
 
     def _signatures(self):
@@ -322,7 +343,7 @@ class _Printer:
             P += [f'const IDX f_{a}' for a in 'czyx'] if s.ff else []
             P += [f'const IDX w_{a}' for a in 'zyx'] if s.of else []
             # (with an ω field the scalar rate is not what the collision reads: the cell loads ``omega``)
-            return P + [f'const long long {p}_bytes' for p in pdfs] + [f'const {self.ct} omega{"_s" if s.of else ""}']
+            return P + [f'const long long {p}_bytes' for p in pdfs] + [f'const {self.ct} {self.om_arg}']
         force = ['const T* __restrict__ force'] if s.ff else []
         omf = ['const T* __restrict__ omf'] if s.of else []
         rho = ['T* __restrict__ out', 'const unsigned* __restrict__ nbmask', 'const T* __restrict__ rho_adj',
@@ -353,6 +374,7 @@ class _Printer:
         if s.hip:
             L.append('typedef unsigned u32x2 __attribute__((ext_vector_type(2)));')
         self.link_tables(L)
+        self.smagorinsky_rate(L)
         self.forward_cell(L)
         self.adjoint_cell(L)
         if s.two:
@@ -478,7 +500,7 @@ class _Printer:
         if not self.s.of:
             return
         L.append('  const IDX wc = ' + ' + '.join(f'(IDX){a} * w_{a}' for a in self.axes) + ';')
-        L.append(f'  const {self.ct} omega = ({self.ct})omf[wc];')
+        L.append(f'  const {self.ct} {self.om0} = ({self.ct})omf[wc];')
 
     def pull_loads(self, L, progs=True, hoisted=False):
         """``f_i``: the pulled pdfs of the cell — ``src_i(x − c_i)``, or the link of the wall cell there (bounce-back
@@ -550,6 +572,7 @@ class _Printer:
             m = f'(m{a} + {half})' if s.fm == 'guo' else f'm{a}'      # Guo: velocity shifted by F/2
             L.append(f'  const {ct} u{a} = {m}' + (' * irho;' if s.compressible else ';'))
         L.append(f'  const {ct} usq = ' + ' + '.join(f'u{a} * u{a}' for a in range(D)) + ';')
+        self.smagorinsky_moments(L)
         if s.fm == 'guo':
             L.append(f'  const {ct} uF = ' + ' + '.join(f'u{a} * {self.Fa(a)}' for a in range(D)) + ';')
             L.append(f'  const {ct} kg = ({ct})1 - ({ct})0.5 * omega;')
@@ -561,6 +584,86 @@ class _Printer:
                 wo = self.c_(s.trt[1])
             L.append(f'  const {ct} w_odd = {wo};')
             L.append(f'  const {ct} ta = ({ct})0.5 * (omega + w_odd), tb = ({ct})0.5 * (omega - w_odd);')
+
+    # ---- the Smagorinsky subgrid model
+    def smagorinsky_rate(self, L):
+        """``lbm_omega_eff``, the one definition of the effective rate: ``ω_eff = 2 / (τ0 + R)``, ``τ0 = 1/ω0``,
+        ``R = √(τ0² + 18 C_s² q)`` (R is returned too: the adjoint's chain factors read it)."""
+        s, ct = self.s, self.ct
+        if s.sm is None:
+            return
+        sqrt = '__builtin_sqrt' if ct == 'double' else '__builtin_sqrtf'
+        L.append(f'{self.fn} {ct} lbm_omega_eff(const {ct} omega_0, const {ct} q, {ct}* R)\n{{')
+        L.append(f'  const {ct} tau0 = ({ct})1 / omega_0;')
+        L.append(f'  *R = {sqrt}(tau0 * tau0 + {self.c_(18 * s.sm * s.sm)} * q);')
+        L.append(f'  return ({ct})2 / (tau0 + *R);\n}}')
+
+    def smagorinsky_moments(self, L):
+        """After ρ, u: ``Π_ab = Σ_i c_ia c_ib (f_i − feq_i)`` with the equilibrium's closed second moments
+        ``ρ (δ_ab/3 + u_a u_b)`` (incompressible: ``ρ δ_ab/3 + u_a u_b``; exact for the second-order equilibrium on
+        D2Q9, D3Q19 and D3Q27, whose weights are isotropic to fourth order), ``N = √(2 Σ_ab Π_ab²)`` over all D²
+        entries, ``q = N/ρ`` (incompressible: ``N``) and ``omega``, the rate everything below reads."""
+        s, ct, D = self.s, self.ct, self.D
+        if s.sm is None:
+            return
+        sqrt = '__builtin_sqrt' if ct == 'double' else '__builtin_sqrtf'
+        third = self.c_(1.0 / 3.0)
+        for a in range(D):
+            for b in range(a, D):
+                pos = [f'f{i}' for i, c in enumerate(self.dirs) if c[a] * c[b] == 1]
+                neg = [f'f{i}' for i, c in enumerate(self.dirs) if c[a] * c[b] == -1]
+                mom = '(' + ' + '.join(pos) + ')' + (' - (' + ' + '.join(neg) + ')' if neg else '')
+                uu = f'u{a} * u{b}'
+                if a == b:
+                    eq = f'rho * ({third} + {uu})' if s.compressible else f'(rho * {third} + {uu})'
+                else:
+                    eq = f'rho * {uu}' if s.compressible else uu
+                L.append(f'  const {ct} sm_P{a}{b} = {mom} - {eq};')
+        diag = ' + '.join(f'sm_P{a}{a} * sm_P{a}{a}' for a in range(D))
+        off = ' + '.join(f'sm_P{a}{b} * sm_P{a}{b}' for a in range(D) for b in range(a + 1, D))
+        L.append(f'  const {ct} sm_N = {sqrt}(({ct})2 * ({diag}) + ({ct})4 * ({off}));')
+        L.append(f'  const {ct} sm_q = sm_N' + (' * irho;' if s.compressible else ';'))
+        L.append(f'  {ct} sm_R;')
+        L.append(f'  const {ct} omega = lbm_omega_eff({self.om0}, sm_q, &sm_R);')
+
+    def sm_P(self, i):
+        """``P_i = Σ_ab Π_ab c_ia c_ib`` of direction i (None for the rest direction, where it is 0)."""
+        c = self.dirs[i]
+        t = [f'sm_P{a}{a}' for a in range(self.D) if c[a]]
+        t += [('- ' if c[a] * c[b] < 0 else '') + f'({self.ct})2 * sm_P{a}{b}'
+              for a in range(self.D) for b in range(a + 1, self.D) if c[a] * c[b]]
+        return '(' + ' + '.join(t).replace('+ - ', '- ') + ')' if t else None
+
+    def smagorinsky_adjoint(self, L):
+        """The chain factors of ``ω_eff(f, ω0)`` once ``dom = Σ_i g_i ∂dst_i/∂ω`` (at ω = ω_eff) is complete:
+
+            v_k += dom ∂ω_eff/∂f_k,   ∂ω_eff/∂f_k = ∂ω_eff/∂q · ∂q/∂f_k,   ∂ω_eff/∂q = −ω_eff² K / (4R),  K = 18 C_s²
+            ∂q/∂f_k = (∂N/∂f_k − q)/ρ  (incompressible: ∂N/∂f_k),   ∂N/∂f_k = (2/N)(P_k − Σ_i P_i ∂feq_i/∂f_k)
+
+        With κ = dom ∂ω_eff/∂q and λ = 2κ/(Nρ) (incompressible: 2κ/N): ``v_k += λ P_k − Σ_i λ P_i ∂feq_i/∂f_k − κ q/ρ``
+        (the last term compressible only). The middle sum has the form of the equilibrium sums of ``adjoint_sums``:
+        they run over ``h_i − λ P_i`` — which is why ``dom`` is finished before them here, not after
+        (``omega_adjoint``). Where N = 0, ∂N/∂f_k is defined as 0 (λ = 0): the reciprocal is guarded, no NaN.
+        With an ω field: ``domega += dom ∂ω_eff/∂ω0``, ``∂ω_eff/∂ω0 = ω_eff² (1 + τ0/R) / (2 ω0²)``."""
+        s, ct = self.s, self.ct
+        if s.sm is None:
+            return
+        self.omega_adjoint_equilibria(L)
+        K = self.c_(18 * s.sm * s.sm)
+        L.append(f'  const {ct} sm_k = -dom * omega * omega * {K} / (({ct})4 * sm_R);')
+        L.append(f'  const {ct} sm_iN = sm_N > ({ct})0 ? ({ct})1 / sm_N : ({ct})0;')
+        L.append(f'  const {ct} sm_l = ({ct})2 * sm_k * sm_iN' + (' * irho;' if s.compressible else ';'))
+        if s.compressible:
+            L.append(f'  const {ct} sm_c = sm_k * sm_q * irho;')
+        if s.of:
+            L.append(f'  domega[wc] += (T)(dom * omega * omega * (({ct})1 + (({ct})1 / {self.om0}) / sm_R) / '
+                     f'(({ct})2 * {self.om0} * {self.om0}));')
+
+    def sm_fold(self, i, hi):
+        """The weight of direction i in the equilibrium sums: ``h_i`` (``hi``), with Smagorinsky ``h_i − λ P_i``."""
+        if self.s.sm is None or not self.sm_P(i):
+            return hi
+        return f'({hi} - sm_l * {self.sm_P(i)})'
 
     def obstacle_copy(self, L, p, off, sp, soff):
         """An obstacle cell keeps its state (forward: ``dst = src``; adjoint: ``out = g``): array ``sp`` at ``soff`` to
@@ -650,6 +753,7 @@ class _Printer:
         self.pull_loads(L, self.adj_progs, hoisted=listed and s.walls)
         self.moments(L)
         self.omega_adjoint_pdfs(L)
+        self.smagorinsky_adjoint(L)
         if s.rho_links:
             L.append(f'  {ct} Rr = 0;')             # Σ_j βρ_j v_j over the cell's density-weighted links
         gown = s.g_own if s.fix else []
@@ -753,7 +857,9 @@ class _Printer:
                 # the equilibrium sums over h_i = a g_i + b g_ī (rest population: ω g_0)
                 hi = f'(ta * g{i} + tb * g{self.inv[i]})' if self.inv[i] != i else f'omega * g{i}'
             else:
-                hi = f'h{i}' if s.mrt is not None else f'g{i}'
+                # (Smagorinsky, SRT: h_i = ω g_i — the scatter then has no ω in front of the equilibrium part)
+                hi = f'h{i}' if s.mrt is not None else f'omega * g{i}' if s.sm is not None else f'g{i}'
+            hi = self.sm_fold(i, hi)
             L.append(f'    const {ct} gw = {hi} * {self.c_(w[i])};')
             L.append('    S += gw;')
             if s.gsplit:
@@ -829,7 +935,7 @@ class _Printer:
         """``omega_field``: the part of ``dω`` that reads the pulled pdfs, ``dom = −Σ_k q_k f_k`` — taken right after
         the moments, so that no ``f_k`` stays live through the adjoint's sums (``omega_adjoint`` has the formulas)."""
         s, ct = self.s, self.ct
-        if not s.of:
+        if not s.of and s.sm is None:
             return
         if s.trt is not None:
             if s.trt[0] == 'magic':
@@ -855,9 +961,15 @@ class _Printer:
         (1 + ω₋′)/2``, ``b′ = (1 − ω₋′)/2``, ``ω₋′ = −16Λ / (4Λω + 2 − ω)²`` (magic number) or 0 (a constant odd rate);
         the rest population ``q_0 = g_0``. MRT ``dst = f − (ω P_ω + C) n``: ``q = P_ωᵀ g``. Guo's term
         ``w_i (1 − ω/2) T_i``, ``T_i = 3 (c_i − u)·F + 9 (c_i·u)(c_i·F)``, adds ``−½ Σ_i g_i w_i T_i``."""
+        s = self.s
+        if not s.of or s.sm is not None:
+            return                                  # (Smagorinsky: ``smagorinsky_adjoint`` has stored it already)
+        self.omega_adjoint_equilibria(L)
+        L.append('  domega[wc] += (T)dom;')
+
+    def omega_adjoint_equilibria(self, L):
+        """``dom += Σ_k q_k feq_k`` and Guo's ``−½ Σ_i g_i w_i T_i`` (``omega_adjoint``)."""
         s, ct, w = self.s, self.ct, self.w
-        if not s.of:
-            return
         if s.fm == 'guo':
             L.append(f'  {ct} domF = 0;')                 # Σ_i g_i w_i T_i
         for i in range(self.Q):
@@ -870,7 +982,6 @@ class _Printer:
             L.append('  }')
         if s.fm == 'guo':
             L.append(f'  dom -= ({ct})0.5 * domF;')
-        L.append('  domega[wc] += (T)dom;')
 
     def scatter(self, L, j):
         """``v_j``, stored to the cell the forward pulled ``f_j`` from — ``(x − c_j, j)``, or ``(x, ī)`` for a bounced
@@ -882,12 +993,17 @@ class _Printer:
         du = f'(({cbs}) - Bu) * irho' if s.compressible else f'({cbs})'
         linked = s.walls and any(self.dirs[j]) and s.links is not None
         vq = '' if linked else 'const '
+        # Smagorinsky: + dom ∂ω_eff/∂f_j beside the folded sums (``smagorinsky_adjoint``)
+        sm = '' if s.sm is None else (f' + sm_l * {self.sm_P(j)}' if self.sm_P(j) else '') + \
+            (' - sm_c' if s.compressible else '')
         if s.trt is not None and inv[j] != j:
-            L.append(f'  {{ {vq}{ct} v = (({ct})1 - ta) * g{j} - tb * g{inv[j]} + (A + {du});')
+            L.append(f'  {{ {vq}{ct} v = (({ct})1 - ta) * g{j} - tb * g{inv[j]} + (A + {du}){sm};')
         elif s.trt is not None:
-            L.append(f'  {{ {vq}{ct} v = (({ct})1 - omega) * g{j} + (A + {du});')
+            L.append(f'  {{ {vq}{ct} v = (({ct})1 - omega) * g{j} + (A + {du}){sm};')
         elif s.mrt is not None:
-            L.append(f'  {{ {vq}{ct} v = g{j} - h{j} + (A + {du});')
+            L.append(f'  {{ {vq}{ct} v = g{j} - h{j} + (A + {du}){sm};')
+        elif s.sm is not None:
+            L.append(f'  {{ {vq}{ct} v = (({ct})1 - omega) * g{j} + (A + {du}){sm};')
         else:
             L.append(f'  {{ {vq}{ct} v = (({ct})1 - omega) * g{j} + omega * (A + {du});')
         taken = ''                  # (fix-up kernel) guard of the scatter store: not where a neighbour link is taken
@@ -1077,7 +1193,7 @@ class _Printer:
             adj, n = k == 'adj', len(pdfs)
             L.append(f'void lbm_{k}(void** P, const i64* N, const i64* S, const i64* B_, const double* Dv)\n{{')
             L.append('  (void)B_; const int Z = (int)N[0], Y = (int)N[1], X = (int)N[2];')
-            L.append(f'  const {ct} omega{"_s" if s.of else ""} = ({ct})Dv[0];')
+            L.append(f'  const {ct} {self.om_arg} = ({ct})Dv[0];')
             ptrs = [('const T*', ARRAYS[p]) for p in pdfs[:-1]] + [('T*', ARRAYS[pdfs[-1]])] + \
                 [('const unsigned*', 'nbmask'), ('const unsigned char*', 'wallid')]
             L.append('  ' + ' '.join(f'{ty} {nm} = ({ty})P[{i}];' for i, (ty, nm) in enumerate(ptrs)))

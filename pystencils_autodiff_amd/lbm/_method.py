@@ -153,6 +153,41 @@ def relaxation_rate_from_magic_number(relaxation_rate, magic_number=sp.Rational(
 
 METHODS = ('srt', 'trt', 'mrt')
 
+SMAGORINSKY_DEFAULT = sp.Rational(12, 100)
+
+
+def smagorinsky_constant(smagorinsky):
+    """C_s of the ``smagorinsky`` keyword: None (off) for ``False`` / ``None``, 0.12 for ``True``, a positive number,
+    or a sympy symbol; anything else is a ``ValueError``."""
+    if smagorinsky is None or smagorinsky is False:
+        return None
+    if smagorinsky is True:
+        return SMAGORINSKY_DEFAULT
+    if isinstance(smagorinsky, sp.Symbol):
+        return smagorinsky
+    if isinstance(smagorinsky, (int, float, sp.Integer, sp.Float, sp.Rational)) and smagorinsky > 0:
+        return sp.sympify(smagorinsky)
+    raise ValueError(f'smagorinsky={smagorinsky!r}: False, True (C_s = 0.12), a positive number or a sympy symbol')
+
+
+def smagorinsky_rate(stencil, f, feq, rho, omega0, cs, compressible, omega_eff=sp.Symbol('omega_eff')):
+    """The subexpressions of the Smagorinsky model's effective rate from the pulled pdfs ``f``, their equilibria
+    ``feq`` and the density symbol: ``smag_Pi_ab`` (a ≤ b), ``smag_N``, ``smag_q``, ``smag_R``, ``omega_eff``."""
+    D = stencil.D
+    Pi = {}
+    out = []
+    for a in range(D):
+        for b in range(a, D):
+            Pi[a, b] = Pi[b, a] = sp.Symbol(f'smag_Pi_{a}{b}')
+            out.append(ps.Assignment(Pi[a, b], sum(c[a] * c[b] * (fi - fe)
+                                                   for c, fi, fe in zip(stencil.directions, f, feq) if c[a] * c[b])))
+    N, q, R = sp.symbols('smag_N smag_q smag_R')
+    out.append(ps.Assignment(N, sp.sqrt(2 * sum(Pi[a, b] ** 2 for a in range(D) for b in range(D)))))
+    out.append(ps.Assignment(q, N / rho if compressible else N))
+    out.append(ps.Assignment(R, sp.sqrt(1 / omega0 ** 2 + 18 * cs ** 2 * q)))
+    out.append(ps.Assignment(omega_eff, 2 / (1 / omega0 + R)))
+    return out
+
 # MRT moment polynomials (exponents per axis), grouped by relaxation rate: lbmpy's weighted-orthogonal MRT groups
 # (shear, bulk, third order, fourth order) [ext]; conserved moments (density, momentum) first
 _MRT_POLYS = {
@@ -222,7 +257,7 @@ def mrt_relaxation_matrices(stencil):
 def create_lb_update_rule(stencil='D2Q9', relaxation_rate=None, compressible=False, src_field=None, dst_field=None,
                           data_type='float64', layout='fzyx', kernel_type='stream_pull_collide', force_model=None,
                           force=None, method='srt', relaxation_rates=None, magic_number=sp.Rational(3, 16),
-                          zero_centered=False):
+                          zero_centered=False, smagorinsky=False):
     """SRT (BGK) or TRT ``stream_pull_collide`` update rule (lbmpy ``create_lb_update_rule(stencil=…,
     method='srt' | 'trt', relaxation_rate=…, compressible=…, kernel_type='stream_pull_collide')`` [ext]).
     ``relaxation_rate`` = ω: a number, or a sympy symbol left as a kernel parameter (default: the symbol ``omega``).
@@ -250,7 +285,17 @@ def create_lb_update_rule(stencil='D2Q9', relaxation_rate=None, compressible=Fal
     ``zero_centered``: the pdf fields hold ``δf_i = f_i − w_i`` (lbmpy's zero-centred storage [ext], background
     density 1) — the pulled values are ``f_i = src_i(x − c_i) + w_i`` and the rule assigns ``dst_i ← (collision + force
     term)_i − w_i``: the stored numbers are of the size of the flow's signal, not of the weights, which is what makes
-    ``data_type='float16'`` pdfs usable (``ac.zero_centered``; the macroscopic getter / setter take the same flag)."""
+    ``data_type='float16'`` pdfs usable (``ac.zero_centered``; the macroscopic getter / setter take the same flag).
+
+    ``smagorinsky``: the Smagorinsky subgrid model (lbmpy's ``smagorinsky=C_s`` [ext]) — ``False`` / ``None`` off,
+    ``True`` C_s = 0.12, a positive number, or a sympy symbol (a kernel parameter). The rate becomes a function of the
+    cell's own pulled pdfs (``smagorinsky_rate``): with n = f − feq, Π_ab = Σ_i c_ia c_ib n_i, N = √(2 Σ_ab Π_ab²),
+    q = N/ρ (incompressible: N), τ0 = 1/ω, R = √(τ0² + 18 C_s² q): ``ω_eff = 2 / (τ0 + R)`` replaces ω wherever the
+    collision reads it (the SRT rate, TRT's even rate and the odd one derived from it by the magic number, the MRT groups
+    relaxing with ω, Guo's 1 − ω/2); constant TRT odd / MRT rates stay constant. The subexpressions ``smag_Pi_ab``,
+    ``smag_N``, ``smag_q``, ``smag_R`` and ``omega_eff`` carry it (``ac.smagorinsky``: C_s; ``ac.relaxation_rate`` stays
+    ω). At N = 0 the symbolic derivative of the square root is 0/0: the rule's AutoDiffOp kernels give NaN there, the
+    lattice kernels define ∂N/∂f = 0 (a uniform rest state then has the plain model's gradient)."""
     if kernel_type != 'stream_pull_collide':
         raise NotImplementedError("only kernel_type='stream_pull_collide' is restated")
     method = str(method).lower()
@@ -275,6 +320,12 @@ def create_lb_update_rule(stencil='D2Q9', relaxation_rate=None, compressible=Fal
     shift, term = _force(force_model, force, st)
     rho, us, subs = _moments(st, f, compressible, shift)
     feq = [_feq(st, i, rho, us, compressible) for i in range(st.Q)]
+    cs = smagorinsky_constant(smagorinsky)
+    omega0 = omega
+    if cs is not None:
+        # every use of ω below reads the effective rate
+        omega = sp.Symbol('omega_eff')
+        subs += smagorinsky_rate(st, f, feq, rho, omega0, cs, compressible, omega)
     mrt_rates = None
     if method == 'srt':
         omega_odd = None
@@ -282,10 +333,12 @@ def create_lb_update_rule(stencil='D2Q9', relaxation_rate=None, compressible=Fal
     elif method == 'mrt':
         omega_odd = None
         given = list(relaxation_rates or [])
-        mrt_rates = {g: (sp.sympify(given[n]) if n < len(given) else omega) for n, g in enumerate(MRT_GROUPS)}
+        mrt_rates = {g: (sp.sympify(given[n]) if n < len(given) else omega0) for n, g in enumerate(MRT_GROUPS)}
+        # (Smagorinsky: the groups relaxing with ω relax with ω_eff)
+        rates = {g: (omega if r == omega0 else r) for g, r in mrt_rates.items()}
         P = mrt_relaxation_matrices(st)
         neq = [f[k] - feq[k] for k in range(st.Q)]
-        coll = [f[i] - sum(mrt_rates[g] * sum(P[g][i][k] * neq[k] for k in range(st.Q) if P[g][i][k] != 0)
+        coll = [f[i] - sum(rates[g] * sum(P[g][i][k] * neq[k] for k in range(st.Q) if P[g][i][k] != 0)
                            for g in MRT_GROUPS) for i in range(st.Q)]
     else:
         omega_odd = sp.sympify(relaxation_rates[1]) if relaxation_rates is not None else \
@@ -300,7 +353,8 @@ def create_lb_update_rule(stencil='D2Q9', relaxation_rate=None, compressible=Fal
     ac.stencil = st
     ac.zero_centered = bool(zero_centered)
     ac.compressible = compressible
-    ac.relaxation_rate = omega
+    ac.relaxation_rate = omega0
+    ac.smagorinsky = cs
     ac.method = method
     ac.relaxation_rate_odd = omega_odd
     ac.magic_number = sp.sympify(magic_number) if method == 'trt' and relaxation_rates is None else None

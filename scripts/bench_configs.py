@@ -236,7 +236,7 @@ def run_slab(name, builder, shape, dtype, full_cells, steps=20, warmup=3):
 
 
 def run_lbm(name, stencil, shape, dtype, T=10, reps=5, compressible=False, walls=False, force_model=None,
-            force_field=False, method='srt', omega_field=False, zero_centered=False):
+            force_field=False, method='srt', omega_field=False, zero_centered=False, smagorinsky=False):
     """Lattice Boltzmann time-step op (lbm.AutoDiffLatticeBoltzmannStep.create_timestep_op): T forward steps
     and the T adjoint steps, HIP events around Op.apply and backward (back-to-back applies). MLUPS = cells · T / time; algorithmic
     bytes per cell and step: forward 2q·s (read src, write dst), adjoint 3q·s (read diffdst and the recorded
@@ -245,7 +245,8 @@ def run_lbm(name, stencil, shape, dtype, T=10, reps=5, compressible=False, walls
     (the force read), + 3·D·s adjoint (the force read, its accumulated adjoint read and written).
     ``omega_field``: the relaxation rate per cell (a scalar field, an input of the op): + s forward (the ω read), + 3·s
     adjoint (the ω read, its accumulated adjoint read and written) — (2q + 1)·s and (3q + 3)·s.
-    ``zero_centered``: the pdf arrays hold f − w (the float16 rows; s = 2 there)."""
+    ``zero_centered``: the pdf arrays hold f − w (the float16 rows; s = 2 there).
+    ``smagorinsky``: the Smagorinsky constant C_s (the effective rate from the cell's own pdfs: no bytes of its own)."""
     import sympy as sp
     import torch
 
@@ -260,7 +261,7 @@ def run_lbm(name, stencil, shape, dtype, T=10, reps=5, compressible=False, walls
     if omega_field:
         mk['relaxation_rate'] = ps.fields(f"omega_f: {dts}[{D}D]").center
     rule = lbm.create_lb_update_rule(stencil, compressible=compressible, data_type=dts, force_model=force_model,
-                                     force=force, zero_centered=zero_centered, **mk)
+                                     force=force, zero_centered=zero_centered, smagorinsky=smagorinsky, **mk)
     step = lbm.AutoDiffLatticeBoltzmannStep(rule, domain_size=shape, relaxation_rate=None if omega_field else 1.5,
                                             target='gpu')
     if walls == 'freeslip':
@@ -346,6 +347,8 @@ def run_lbm(name, stencil, shape, dtype, T=10, reps=5, compressible=False, walls
         res['zero_centered'] = True
     if omega_field:
         res['omega'] = 'per-cell field'
+    if smagorinsky:
+        res['smagorinsky'] = smagorinsky
     res['fwd_frac'] = round(res['fwd_GBps'] / PEAK, 4)
     res['bwd_frac'] = round(res['bwd_GBps'] / PEAK, 4)
     print(json.dumps(res))
@@ -454,13 +457,22 @@ def main():
             ('lbm_d2q9_f16_2048^2', 'D2Q9', (2048, 2048), torch.float16, False, 'srt', False, True),
             ('lbm_d3q19_f16_192^3', 'D3Q19', (192, 192, 192), torch.float16, False, 'srt', False, True),
             ('lbm_d2q9_f16_2048^2_channel', 'D2Q9', (2048, 2048), torch.float16, True, 'srt', False, True),
-            ('lbm_d3q19_f16_192^3_channel', 'D3Q19', (192, 192, 192), torch.float16, True, 'srt', False, True)]
+            ('lbm_d3q19_f16_192^3_channel', 'D3Q19', (192, 192, 192), torch.float16, True, 'srt', False, True),
+            # the Smagorinsky subgrid model (C_s = 0.12), with a scalar ω and with the ω field
+            ('lbm_d2q9_f32_2048^2_smagorinsky', 'D2Q9', (2048, 2048), torch.float32, False, 'srt', False, False, 0.12),
+            ('lbm_d3q19_f32_192^3_smagorinsky', 'D3Q19', (192, 192, 192), torch.float32, False, 'srt', False, False,
+             0.12),
+            ('lbm_d2q9_f32_2048^2_smagorinsky_omega_field', 'D2Q9', (2048, 2048), torch.float32, False, 'srt', True,
+             False, 0.12),
+            ('lbm_d3q19_f32_192^3_smagorinsky_omega_field', 'D3Q19', (192, 192, 192), torch.float32, False, 'srt', True,
+             False, 0.12)]
     for name, stencil, shape, dt, walls, *more in lbms:
         if only and name not in only:
             continue
         for _ in range(repeat):
             run_lbm(name, stencil, shape, dt, walls=walls, method=more[0] if more else 'srt',
-                    omega_field=len(more) > 1 and more[1], zero_centered=len(more) > 2 and more[2])
+                    omega_field=len(more) > 1 and more[1], zero_centered=len(more) > 2 and more[2],
+                    smagorinsky=more[3] if len(more) > 3 else False)
 
 
 if __name__ == '__main__':
