@@ -211,9 +211,9 @@ def _compute(H, ind, st):
             def el(e):
                 return f'{_hname(st, fn, jr, e // 2)}[{e % 2}]'
             B.append(f'{ind}const f32x2 {_pname(fn, jr, e0)} = {{(float){el(e0)}, (float){el(e0 + 2)}}};')
-    # (a kernel without z radius assigns slot 0, which nothing declares: its source is pinned as it stands)
+    # (a kernel without z radius has no accumulator slots: its one value per cell pair is declared where it is formed)
     before, after = retirement_lines(ind, H.g['RZ'], H.groups, lambda gr, k: _acc(gr, 0 if k == 't' else k), H.terms,
-                                     '(f32x2)(0)')
+                                     '(f32x2)(0)', temp='const f32x2 ')
     return B + before + _stores(H, ind) + after
 
 
