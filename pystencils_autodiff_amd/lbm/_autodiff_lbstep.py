@@ -37,7 +37,7 @@ import sympy as sp
 from .. import ps
 from ..autodiff import AutoDiffOp
 from ._lattice_kernels import LatticeKernels, fix_cells, neighbour_mask
-from ._lattice_source import density_links_message
+from ._lattice_source import density_links_message, link_rows
 from ._method import LBStencil
 from .boundaries import (AdjointBoundaryCondition, AdjointNoSlip, Boundary, BoundaryHandling, LBMethodView,  # noqa: F401
                          NoSlip, link_form)
@@ -74,8 +74,8 @@ def _lattice_sweeps(step, which, launches, force=None, dforce=None, omf=None, do
     rho = K.rho_buffer(launches[0][0]) if which == 'adj' and K.link_pass else None
     if which != 'adj':
         dforce = domf = None
-    # once: the launches differ in their pdf arrays only
-    mptr = K.tail_ptrs(which, mask, ids, force, dforce, rho, omf, domf)
+    # once: the launches differ in their pdf arrays only (the leading pointer slots)
+    mptr = K.pointers(which, K.operands((), mask, ids, force, dforce, omf, domf, rho))[len(launches[0]):]
     plans = {}
     for ts in launches:
         sig = tuple(t.stride() for t in ts)
@@ -87,7 +87,7 @@ def _lattice_sweeps(step, which, launches, force=None, dforce=None, omf=None, do
         K.fix_launch(which, list(ts), mask, om, ids, force, dforce, cells, stream, omf, domf)
         if rho is not None:
             # the second pass of density-weighted walls (and, on the CPU, link programs) on this launch's output
-            K.rho_pass(ts[2], mask, rho, ts[0], ids, stream)
+            K.rho_pass(ts[2], mask, rho, stream)
 
 
 def _plain_force_field(force, D):
@@ -452,7 +452,7 @@ class AutoDiffLatticeBoltzmannStep:
         # links that read a density (density-weighted, link programs, neighbour links) are built for plain float32 /
         # float64 pdfs only (``LatticeSource``)
         reads_density = any(p is not None for p in form) if kind != 'affine' else \
-            any(len(t) > 3 and (t[3] != 0 or t[4] != 0) for t in form)
+            any(t.reads_density for t in link_rows([form])[0])
         if reads_density:
             for on, what in ((getattr(self._update_rule, 'zero_centered', False), 'zero_centered pdfs'),
                              (np.dtype(self.pdf_field.dtype.numpy_dtype) == np.float16, 'float16 pdfs')):

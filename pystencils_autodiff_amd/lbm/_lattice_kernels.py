@@ -26,7 +26,8 @@ What this schedule does differently:
 
 One source is printed for both targets (``_lattice_source``): a HIP kernel (one thread per cell, wave64 along x)
 compiled by hiprtc, and a C loop nest (``use_cuda=False`` / ``target='cpu'``) compiled by gcc. This module holds the
-host side: masks and cell lists, compiling, argument buffers and launches.
+host side: masks and cell lists, compiling, argument buffers and launches. Every argument buffer is laid out by the
+printer's own table of the kernel's arguments (``_lattice_source.args.kernel_args``) and filled by name.
 """
 import ctypes
 import dataclasses
@@ -35,7 +36,9 @@ import struct
 
 import numpy as np
 
-from ._lattice_source import FIX_BIT, FIX_BLOCK, SELF_BIT, LatticeSource, emit  # noqa: F401 (the bits: re-exported)
+from ._lattice_source import FIX_BIT, FIX_BLOCK, SELF_BIT  # noqa: F401 (the bits: re-exported)
+from ._lattice_source import ARRAYS, LatticeSource, emit, kernel_args, link_programs, struct_format
+from ._lattice_source.args import CELLS, EXTENT, KERNELS, POINTER, RATE, REACH, STRIDE
 
 __all__ = ['LatticeKernels', 'LaunchPlan', 'lattice_strides', 'row_interleaved_empty', 'neighbour_mask']
 
@@ -53,13 +56,13 @@ def fix_cells(flags, stencil, program_ids, programs=None):
         if any(c):
             near |= np.roll(prog, tuple(int(v) for v in c), axis=axes)
     fluid = f == 0
-    for wid, pg in enumerate(programs or ()):
-        for d, row in enumerate(pg or ()):
-            if row is None or len(row) < 4 or not row[3]:
+    for wid, wall in enumerate(link_programs(programs)):
+        for d, pg in enumerate(wall or ()):
+            if pg is None or not pg.reads:
                 continue
             # the fluid cells x whose link of direction d ends in a wall cell of this id: x + c_d
             src = fluid & np.roll(f == wid, tuple(-int(v) for v in stencil.directions[d]), axis=axes)
-            for o in row[3]:
+            for o in pg.reads:
                 near |= np.roll(src, tuple(int(v) for v in stencil.directions[o]), axis=axes)
     return near & fluid
 
@@ -88,14 +91,29 @@ def neighbour_mask(flags, stencil, xp, fix=None):
     return m.to(xp.int32).contiguous() if is_torch else np.ascontiguousarray(m.astype(np.uint32))
 
 
+def _element_strides(t):
+    """Strides in elements of a torch tensor or a numpy array."""
+    return [int(s) for s in (t.stride() if hasattr(t, 'stride') and callable(t.stride) else
+                             [s // t.itemsize for s in t.strides])]
+
+
 def lattice_strides(t, D):
     """``(s_q, s_z, s_y, s_x)`` in elements of a pdf tensor ``[*spatial, q]`` (2-D: ``s_z`` = 0)."""
-    st = [int(s) for s in (t.stride() if hasattr(t, 'stride') and callable(t.stride) else
-                           [s // t.itemsize for s in t.strides])]
-    sp_ = st[:D]
-    if D == 2:
-        sp_ = [0] + sp_
-    return (st[D],) + tuple(sp_)
+    st = _element_strides(t)
+    return (st[D],) + (0,) * (3 - D) + tuple(st[:D])
+
+
+def _stride_values(ops, D):
+    """name → value of every stride argument the operands ``ops`` give: ``{p}_{q,z,y,x}`` of the pdf arrays,
+    ``f_{c,z,y,x}`` of the force field, ``w_{z,y,x}`` of the ω field (2-D: the z strides are 0)."""
+    v = {}
+    for p, t in [(p, ops.get(name)) for p, name in ARRAYS.items()] + [('f', ops.get('force'))]:
+        if t is not None:
+            v.update(zip((f'{p}_c' if p == 'f' else f'{p}_q', f'{p}_z', f'{p}_y', f'{p}_x'), lattice_strides(t, D)))
+    if ops.get('omf') is not None:
+        sw = _element_strides(ops['omf'])
+        v.update(zip(('w_z', 'w_y', 'w_x'), [0] * (3 - len(sw)) + sw))
+    return v
 
 
 def row_interleaved_empty(domain, Q, dtype, device):
@@ -155,14 +173,29 @@ class LatticeKernels:
         self._rho_bufs = {}
         self._fns = {}
         self._plans = {}
+        # every kernel's arguments as the printer declares them (the same for every index type and addressing
+        # mode), and the names of the pointers among them, which a launch patches (``lbm_adj_fix``: ``lbm_adj``'s)
+        self._tables = {k: kernel_args(self._spec(fix=k == 'adj_fix'), k) for k in KERNELS}
+        self._ptr_names = {k: tuple(a.name for a in t if a.kind == POINTER) for k, t in self._tables.items()}
+
+    def _spec(self, idx='int', addr='buf', fix=False):
+        """What ``source`` prints: the C spec (inline link programs), or of a HIP module: the main kernels, or
+        (``fix``) the fix-up kernels of the cells next to link-program walls."""
+        if self.target != 'gpu':
+            return self.spec
+        mode = 'fix' if fix else 'main' if self.programs is not None else 'inline'
+        return dataclasses.replace(self.spec, idx=idx, addr=addr, mode=mode)
 
     def source(self, idx='int', addr='buf', fix=False):
-        """The C source (inline link programs), or a HIP module: the main kernels, or (``fix``) the fix-up kernels
-        of the cells next to link-program walls."""
-        if self.target != 'gpu':
-            return emit(self.spec)
-        mode = 'fix' if fix else 'main' if self.programs is not None else 'inline'
-        return emit(dataclasses.replace(self.spec, idx=idx, addr=addr, mode=mode))
+        return emit(self._spec(idx, addr, fix))
+
+    def table(self, kernel):
+        """The arguments of ``lbm_{kernel}`` ('fwd' / 'adj' / 'adj_rho' / 'adj_fix')."""
+        return self._tables[kernel]
+
+    def arg_format(self, kernel, idx):
+        """The ``struct`` codes of ``lbm_{kernel}``'s argument buffer (``_pack``) with strides of type ``idx``."""
+        return struct_format(self.table(kernel), idx, self.ct)
 
     # -- GPU ---------------------------------------------------------------------------------------
     def _gpu_fn(self, which, idx, addr, device):
@@ -210,18 +243,35 @@ class LatticeKernels:
         if min(shape[:-1]) < 2:
             raise ValueError('the periodic lattice needs at least 2 cells per axis')
 
-    def tail_ptrs(self, which, mask, ids, force=None, dforce=None, scratch=None, omf=None, domf=None):
-        """The pointers after the pdf arrays in the argument list of ``lbm_fwd`` / ``lbm_adj`` / ``lbm_adj_fix``: mask,
-        ids, then force[, dforce], then the ω field[, its adjoint], then the second pass's scratch array (None: a slot
-        patched per launch). Torch tensors, or numpy arrays on the C path."""
-        ptrs = (_ptr(mask), _ptr(ids))
-        if force is not None:
-            ptrs += (_ptr(force),) + ((_ptr(dforce),) if which == 'adj' else ())
-        if omf is not None:
-            ptrs += (_ptr(omf),) + ((_ptr(domf),) if which == 'adj' else ())
-        if which == 'adj' and self.link_pass:
-            ptrs += (_ptr(scratch),)
-        return ptrs
+    @staticmethod
+    def operands(tensors, mask, ids, force=None, dforce=None, omf=None, domf=None, scratch=None):
+        """Argument name → operand (torch tensors, or numpy arrays on the C path; None: not given) of ``lbm_fwd``
+        (``tensors``: src, dst) or ``lbm_adj`` / ``lbm_adj_fix`` (src, g, out)."""
+        return dict(zip(('src', 'dst') if len(tensors) == 2 else ('src', 'g', 'out'), tensors), nbmask=mask,
+                    wallid=ids, force=force, dforce=dforce, omf=omf, domega=domf, rho_adj=scratch)
+
+    def pointers(self, kernel, ops):
+        """The pointer slots a launch of ``lbm_{kernel}`` patches, in the table's order, from the operands ``ops``
+        (0 for one not given)."""
+        return tuple(_ptr(ops.get(n)) for n in self._ptr_names[kernel])
+
+    def _values(self, table, ops, omega=None):
+        """The value of every argument of ``table`` from the operands ``ops`` (a pointer not given: 0, a slot patched
+        per launch)."""
+        strides = _stride_values(ops, self.stencil.D)
+        extent = dict(zip('ZYX', self._extent(ops[table[0].name])))
+        vals = []
+        for a in table:
+            if a.kind in (POINTER, CELLS):
+                vals.append(_ptr(ops.get(a.name)))
+            elif a.kind in (EXTENT, STRIDE):
+                vals.append(extent[a.name] if a.kind == EXTENT else strides[a.name])
+            elif a.kind == REACH:
+                t = ops[ARRAYS[a.name[0]]]
+                vals.append(self._reach(t) * t.element_size())
+            else:
+                vals.append(float(omega) if a.kind == RATE else int(ops['cells'].numel()))
+        return vals
 
     @staticmethod
     def _reach(t):
@@ -248,73 +298,31 @@ class LatticeKernels:
             idx = 'long long'
         return idx, addr
 
-    def _arg_format(self, idx, ntensors, nptr, nstrides, fix=False):
-        """``(fmt, index of ω)`` of a ``plan()`` launch's argument buffer (``_pack``): ``nptr`` pointers, the
-        extents, ``nstrides`` strides of type ``idx``, the ``ntensors`` pdf arrays' byte reaches, ω; the fix-up
-        kernel's cell list and its length after them."""
-        code = 'i' if idx == 'int' else 'q'
-        fmt = 'Q' * nptr + 'iii' + code * nstrides + 'q' * ntensors + ('d' if self.ct == 'double' else 'f')
-        return fmt + ('Qi' if fix else ''), len(fmt) - 1
-
-    def _rho_format(self, idx):
-        """``(fmt, index of the src slot or None)`` of a ``rho_plan()`` launch's argument buffer."""
-        code = 'i' if idx == 'int' else 'q'
-        fmt = 'QQQ' + 'iii' + code * 4
-        if self.programs is None:
-            return fmt, None
-        return fmt + 'QQ' + code * 4, len(fmt)
-
-    def _strides(self, arrays, force, omf=None):
-        """The strides after the extents in every kernel's argument list: of each pdf array, then of the force field,
-        then ``(s_z, s_y, s_x)`` of the ω field (2-D: ``s_z`` = 0)."""
-        st = [n for a in list(arrays) + ([force] if force is not None else [])
-              for n in lattice_strides(a, self.stencil.D)]
-        if omf is not None:
-            sw = [int(v) for v in (omf.stride() if hasattr(omf, 'stride') and callable(omf.stride) else
-                                   [v // omf.itemsize for v in omf.strides])]
-            st += [0] * (3 - len(sw)) + sw
-        return st
-
-    def _omega_check(self, shape, omf, domf, which, xp_tensor=True):
-        """The per-cell relaxation rate (and, for the adjoint, its accumulated adjoint): ``[*domain]`` of the pdf
-        dtype, ``domf`` with the strides of ``omf``; none without an ω field."""
+    def _field_check(self, kind, shape, field, adjoint, which, xp_tensor=True):
+        """A per-cell field ``kind`` — 'force': ``[*domain, D]``, 'omega' (the relaxation rate): ``[*domain]`` — and, for
+        the adjoint kernel, its accumulated adjoint: both of the pdf dtype, ``adjoint`` with the strides of ``field``;
+        none where the kernels take no such field."""
         D = self.stencil.D
-        need = [omf] + ([domf] if which == 'adj' else [])
-        if not self.omega_field:
-            if omf is not None or domf is not None:
-                raise ValueError('these lattice kernels take no relaxation-rate field')
+        on, want = (self.force_field, tuple(shape[:D]) + (D,)) if kind == 'force' else \
+            (self.omega_field, tuple(shape[:D]))
+        what, kernels, name, short = ('force field', 'force-field', 'force', 'force') if kind == 'force' else \
+            ('relaxation-rate field', 'ω-field', 'relaxation-rate field', 'relaxation-rate')
+        need = [field] + ([adjoint] if which == 'adj' else [])
+        if not on:
+            if field is not None or adjoint is not None:
+                raise ValueError(f'these lattice kernels take no {what}')
             return
         if any(t is None for t in need):
-            raise ValueError('the ω-field lattice kernels need the relaxation-rate field'
+            raise ValueError(f'the {kernels} lattice kernels need the {name}'
                              f'{" and its adjoint" if which == "adj" else ""}')
         for t in need:
-            if tuple(t.shape) != tuple(shape[:D]):
-                raise ValueError(f'relaxation-rate field of shape {tuple(t.shape)}: expected {tuple(shape[:D])}')
+            if tuple(t.shape) != want:
+                raise ValueError(f'{what} of shape {tuple(t.shape)}: expected {want}')
             if (t.dtype != self.dtype) if not xp_tensor else (str(t.dtype).split('.')[-1] != self.dtype.name):
-                raise ValueError(f'relaxation-rate field dtype {t.dtype}: expected {self.dtype}')
-        if which == 'adj' and tuple(domf.stride() if xp_tensor else domf.strides) != \
-                tuple(omf.stride() if xp_tensor else omf.strides):
-            raise ValueError('the relaxation-rate adjoint must have the strides of the relaxation-rate field')
-
-    def _force_check(self, shape, force, dforce, which, xp_tensor=True):
-        """The per-cell force (and, for the adjoint, its accumulated adjoint): ``[*domain, D]`` of the pdf dtype,
-        ``dforce`` with the strides of ``force``; none without a force field."""
-        D = self.stencil.D
-        need = [force] + ([dforce] if which == 'adj' else [])
-        if not self.force_field:
-            if force is not None or dforce is not None:
-                raise ValueError('these lattice kernels take no force field')
-            return
-        if any(t is None for t in need):
-            raise ValueError(f'the force-field lattice kernels need the force{" and its adjoint" if which == "adj" else ""}')
-        for t in need:
-            if tuple(t.shape) != tuple(shape[:D]) + (D,):
-                raise ValueError(f'force field of shape {tuple(t.shape)}: expected {tuple(shape[:D]) + (D,)}')
-            if (t.dtype != self.dtype) if not xp_tensor else (str(t.dtype).split('.')[-1] != self.dtype.name):
-                raise ValueError(f'force field dtype {t.dtype}: expected {self.dtype}')
-        if which == 'adj' and tuple(dforce.stride() if xp_tensor else dforce.strides) != \
-                tuple(force.stride() if xp_tensor else force.strides):
-            raise ValueError('the force adjoint must have the strides of the force')
+                raise ValueError(f'{what} dtype {t.dtype}: expected {self.dtype}')
+        if which == 'adj' and tuple(adjoint.stride() if xp_tensor else adjoint.strides) != \
+                tuple(field.stride() if xp_tensor else field.strides):
+            raise ValueError(f'the {short} adjoint must have the strides of the {name}')
 
     def plan(self, which, tensors, mask, omega, ids=None, force=None, dforce=None, fix=None, omf=None, domf=None):
         """The launch of ``which`` ('fwd' / 'adj') on tensors of these shapes, strides, dtype and device (with or
@@ -330,26 +338,24 @@ class LatticeKernels:
         plan = self._plans.get(key)
         if plan is not None:
             return plan
-        self._force_check(tuple(tensors[0].shape), force, dforce, which)
-        self._omega_check(tuple(tensors[0].shape), omf, domf, which)
+        self._field_check('force', tuple(tensors[0].shape), force, dforce, which)
+        self._field_check('omega', tuple(tensors[0].shape), omf, domf, which)
         self._check(tensors, mask, ids)
         if any(t is not None and (not t.is_cuda or t.device != tensors[0].device) for t in (omf, domf)):
             raise ValueError('the relaxation-rate field must be on the pdf tensors\' device')
-        strides = self._strides(tensors, force, omf)
         idx, addr = self._launch_mode(tensors, force, dforce, omf, domf)
         dev = tensors[0].device.index
-        fn = self._gpu_fn(which + ('_fix' if fix is not None else ''), idx, addr, dev)
+        # (the fix-up kernel: the cell list and its length after the main kernel's arguments)
+        kernel = which + ('_fix' if fix is not None else '')
+        fn = self._gpu_fn(kernel, idx, addr, dev)
         Z, Y, X = self._extent(tensors[0])
         nblocks = self._blocks(X, Y, Z) if fix is None else -(-int(fix[0].numel()) // FIX_BLOCK)
-        reach = [self._reach(t) * t.element_size() for t in tensors]
-        ptrs = [t.data_ptr() for t in tensors] + list(self.tail_ptrs(which, mask, ids, force, dforce, None, omf, domf))
-        fmt, om_i = self._arg_format(idx, len(tensors), len(ptrs), len(strides), fix is not None)
-        vals = [*ptrs, Z, Y, X, *strides, *reach, float(omega)]
-        if fix is not None:
-            # the fix-up kernel: the cell list and its length after the main kernel's arguments
-            vals += [fix[0].data_ptr(), int(fix[0].numel())]
-        args = _pack(fmt, *vals)
-        plan = self._plans[key] = LaunchPlan(fn, nblocks, args, len(ptrs), dev, _offset(fmt, om_i), fmt[om_i])
+        table = self.table(kernel)
+        fmt = struct_format(table, idx, self.ct)
+        ops = dict(self.operands(tensors, mask, ids, force, dforce, omf, domf), cells=fix[0] if fix else None)
+        om_i = [a.kind for a in table].index(RATE)
+        plan = self._plans[key] = LaunchPlan(fn, nblocks, _pack(fmt, *self._values(table, ops, omega)),
+                                             len(self._ptr_names[which]), dev, _offset(fmt, om_i), fmt[om_i])
         if fix is not None:
             plan.block = FIX_BLOCK
         return plan
@@ -363,8 +369,7 @@ class LatticeKernels:
             return
         plan = self.plan(which, tensors, mask, omega, ids, force, dforce, fix=(cells,), omf=omf, domf=domf)
         rho = self.rho_buffer(tensors[0]) if self.link_pass else None
-        plan(tuple(t.data_ptr() for t in tensors) + self.tail_ptrs(which, mask, ids, force, dforce, rho, omf, domf),
-             stream, omega)
+        plan(self.pointers(which, self.operands(tensors, mask, ids, force, dforce, omf, domf, rho)), stream, omega)
 
     def _scratch_shape(self, domain):
         """Of the second adjoint pass's scratch array: one value per cell (density-weighted links); with inline link
@@ -382,30 +387,22 @@ class LatticeKernels:
             b = self._rho_bufs[key] = torch.empty(self._scratch_shape(key[0]), dtype=t.dtype, device=t.device)
         return b
 
-    def rho_plan(self, out, mask, rho, src=None, ids=None):
-        """The second pass of the adjoint (``lbm_adj_rho``: every component of a cell next to a density-weighted
-        wall gets the cell's Σ_j βρ_j v_j added; with link programs, component k of a cell next to a program wall
-        gets Σ_j J_jk v_j, the Jacobians evaluated at the cell's own pdfs in ``src``) on ``out``'s shape and strides.
-        The plan's pointer slots: out, mask, scratch (+ src, ids with link programs)."""
-        key = ('rho', tuple(out.shape), tuple(out.stride()), out.dtype, out.device) + \
-            ((tuple(src.stride()),) if self.programs is not None else ())
+    def rho_plan(self, out, mask, rho):
+        """The second pass of the adjoint on the HIP target (``lbm_adj_rho``: every component of a cell next to a
+        density-weighted wall gets the cell's Σ_j βρ_j v_j added; link programs run in the fix-up kernel there) on
+        ``out``'s shape and strides. The plan's pointer slots: out, mask, scratch."""
+        key = ('rho', tuple(out.shape), tuple(out.stride()), out.dtype, out.device)
         plan = self._plans.get(key)
         if plan is not None:
             return plan
-        tensors = [out] + ([src] if self.programs is not None else [])
-        idx, addr = self._mode(tensors)
+        idx, addr = self._mode([out])
         dev = out.device.index
         fn = self._gpu_fn('adj_rho', idx, addr, dev)
-        Z, Y, X = self._extent(out)
-        fmt, extra_i = self._rho_format(idx)
-        vals = [out.data_ptr(), mask.data_ptr(), rho.data_ptr(), Z, Y, X, *lattice_strides(out, self.stencil.D)]
-        if self.programs is not None:
-            # the src / ids slots of the inline (C-style) second pass; the HIP ``lbm_adj_rho`` of a lattice with
-            # programs does not take them (its programs run in the fix-up kernel) and ignores the extra bytes
-            vals += [src.data_ptr(), ids.data_ptr(), *lattice_strides(src, self.stencil.D)]
-        plan = self._plans[key] = LaunchPlan(fn, self._blocks(X, Y, Z), _pack(fmt, *vals), 3, dev, None, None)
-        if self.programs is not None:
-            plan.extra = _offset(fmt, extra_i)            # the src / ids slots, patched per launch
+        table = self.table('adj_rho')
+        args = _pack(struct_format(table, idx, self.ct),
+                     *self._values(table, dict(out=out, nbmask=mask, rho_adj=rho)))
+        plan = self._plans[key] = LaunchPlan(fn, self._blocks(*reversed(self._extent(out))), args,
+                                             len(self._ptr_names['adj_rho']), dev, None, None)
         return plan
 
     def forward(self, src, dst, omega, mask=None, stream=None, ids=None, force=None, cells=None, omf=None):
@@ -416,7 +413,7 @@ class LatticeKernels:
             return self._cpu('fwd', [src, dst], omega, mask, ids, force, omf=omf)
         st = _stream(stream, src)
         self.plan('fwd', [src, dst], mask, omega, ids, force, omf=omf)(
-            (src.data_ptr(), dst.data_ptr()) + self.tail_ptrs('fwd', mask, ids, force, omf=omf), st, omega)
+            self.pointers('fwd', self.operands([src, dst], mask, ids, force, omf=omf)), st, omega)
 
     def adjoint(self, src, g, out, omega, mask=None, stream=None, ids=None, force=None, dforce=None, cells=None,
                 omf=None, domf=None):
@@ -427,17 +424,14 @@ class LatticeKernels:
         st = _stream(stream, src)
         rho = self.rho_buffer(src) if self.link_pass else None
         self.plan('adj', [src, g, out], mask, omega, ids, force, dforce, omf=omf, domf=domf)(
-            (src.data_ptr(), g.data_ptr(), out.data_ptr()) +
-            self.tail_ptrs('adj', mask, ids, force, dforce, rho, omf, domf), st, omega)
+            self.pointers('adj', self.operands([src, g, out], mask, ids, force, dforce, omf, domf, rho)), st, omega)
         self.fix_launch('adj', [src, g, out], mask, omega, ids, force, dforce, cells, st, omf, domf)
         if rho is not None:
-            self.rho_pass(out, mask, rho, src, ids, st)
+            self.rho_pass(out, mask, rho, st)
 
-    def rho_pass(self, out, mask, rho, src, ids, stream):
-        """Launch the adjoint's second pass (``rho_plan``) for this launch's ``out`` / ``src``."""
-        plan = self.rho_plan(out, mask, rho, src, ids)
-        plan((out.data_ptr(), mask.data_ptr(), rho.data_ptr()), stream,
-             extra=(src.data_ptr(), ids.data_ptr()) if self.programs is not None else None)
+    def rho_pass(self, out, mask, rho, stream):
+        """Launch the adjoint's second pass (``rho_plan``) for this launch's ``out``."""
+        self.rho_plan(out, mask, rho)(self.pointers('adj_rho', dict(out=out, nbmask=mask, rho_adj=rho)), stream)
 
     def _extent(self, t):
         shape = [int(n) for n in t.shape[:self.stencil.D]]
@@ -467,13 +461,16 @@ class LatticeKernels:
         m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint32)
         idv = None if ids is None else np.ascontiguousarray(ids, dtype=np.uint8)
         shape = self._check_domain(arrays, m, idv)
-        self._force_check(shape, force, dforce, which, xp_tensor=False)
-        self._omega_check(shape, omf, domf, which, xp_tensor=False)
+        self._field_check('force', shape, force, dforce, which, xp_tensor=False)
+        self._field_check('omega', shape, omf, domf, which, xp_tensor=False)
         fn = self._cpu_fn(which)
-        strides = self._strides(arrays, force, omf)
         # the second pass's scratch (both passes in one call)
         rho = np.empty(self._scratch_shape(shape[:D]), self.dtype) if which == 'adj' and self.link_pass else None
-        ptrs = [a.ctypes.data for a in arrays] + list(self.tail_ptrs(which, m, idv, force, dforce, rho, omf, domf))
+        # ``P`` / ``S``: the table's pointers and strides, each in the table's order
+        ops = self.operands(arrays, m, idv, force, dforce, omf, domf, rho)
+        ptrs = self.pointers(which, ops)
+        named = _stride_values(ops, D)
+        strides = [named[a.name] for a in self.table(which) if a.kind == STRIDE]
         ext = list(shape[:D]) if D == 3 else [1] + list(shape[:D])
         P = (ctypes.c_void_p * len(ptrs))(*ptrs)
         N = (ctypes.c_longlong * 3)(*ext)
@@ -487,20 +484,17 @@ class LaunchPlan:
     """One lattice kernel launch with its argument buffer; ``plan(ptrs, stream, omega)`` patches the leading pointer
     slots (the pdf arrays, then the neighbour mask) and the relaxation rate, and launches on the plan's device
     (made current for the launch when it is not: the function handle belongs to that device's module)."""
-    __slots__ = ('fn', 'nblocks', 'template', 'fmt', 'device', 'om_off', 'om_fmt', 'extra', 'block')
+    __slots__ = ('fn', 'nblocks', 'template', 'fmt', 'device', 'om_off', 'om_fmt', 'block')
 
     def __init__(self, fn, nblocks, template, nptr, device, om_off, om_code):
         self.fn, self.nblocks, self.template, self.fmt = fn, nblocks, template, f'<{nptr}Q'
         self.device, self.om_off, self.om_fmt = device, om_off, None if om_code is None else '<' + om_code
-        self.extra = None              # byte offset of two more pointer slots patched per launch (second pass)
         self.block = 256
 
-    def __call__(self, ptrs, stream, omega=None, extra=None):
+    def __call__(self, ptrs, stream, omega=None):
         from ..backends import hip_runtime as rt
         buf = bytearray(self.template)
         struct.pack_into(self.fmt, buf, 0, *ptrs)
-        if extra is not None:
-            struct.pack_into('<2Q', buf, self.extra, *extra)
         if omega is not None and self.om_off is not None:
             struct.pack_into(self.om_fmt, buf, self.om_off, float(omega))
         import torch

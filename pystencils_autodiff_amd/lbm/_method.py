@@ -222,8 +222,8 @@ def mrt_moments(stencil):
     rows = []
     for group, terms in _MRT_POLYS[(st.D, st.Q)]:
         vec = [sp.Integer(0)] * st.Q
-        for t in terms:
-            e, coef = t[:st.D], (sp.Integer(t[st.D]) if len(t) > st.D else sp.Integer(1))
+        for mono in terms:
+            e, coef = mono[:st.D], (sp.Integer(mono[st.D]) if len(mono) > st.D else sp.Integer(1))
             for i, c in enumerate(st.directions):
                 m = sp.Integer(1)
                 for a in range(st.D):

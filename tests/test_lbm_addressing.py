@@ -32,6 +32,17 @@ def _plain_kernels(dtype, **kw):
     return LK.LatticeKernels(lbm.LBStencil('D2Q9'), True, np.dtype(dtype), False, 'gpu', **kw)
 
 
+def _rho_kernels(dtype, programs=False, **kw):
+    """Kernels of a D2Q9 lattice with a density-weighted wall (id 1: the adjoint takes the second pass and its scratch
+    pointer) and, with ``programs``, a link-program wall (id 2). Only their argument tables are read."""
+    plain, rho = (1.0, 0.0, 1.0), (1.0, 0.1, 1.0, 0.05, 0.02)
+    links = ((plain,) * 9, (plain,) + (rho,) * 8) + (((0.0, 0.0, 0.0),) * 9,) * programs
+    progs = (None, None, (None,) + (((), 'c1', ((1, (), '(T)1'),)),) * 8) if programs else None
+    K = LK.LatticeKernels(lbm.LBStencil('D2Q9'), True, np.dtype(dtype), True, 'gpu', links=links, programs=progs, **kw)
+    assert K.rho_links and (K.programs is not None) == programs
+    return K
+
+
 def _meta(reach, dtype, last=2):
     """A meta tensor (no memory) of shape (6, 5, 8, last) whose ``_reach`` is exactly ``reach`` elements."""
     import torch
@@ -214,11 +225,14 @@ def test_plan_argument_buffer_matches_struct(idx, dtype, which, force, scratch, 
     field offset and value; ``LaunchPlan.__call__`` patches the leading pointers and ω at those offsets and nothing
     else."""
     from pystencils_autodiff_amd.backends import hip_runtime as rt
-    K = _plain_kernels(dtype, **(dict(force_model='guo', force_field=True) if force else {}))
+    K = (_rho_kernels if scratch else _plain_kernels)(dtype, **(dict(force_model='guo', force_field=True) if force
+                                                                    else {}))
     ntens = 2 if which == 'fwd' else 3
     nptr = ntens + 2 + ((1 if which == 'fwd' else 2) if force else 0) + int(scratch)
     nstr = 4 * ntens + (4 if force else 0)
-    fmt, om_i = K._arg_format(idx, ntens, nptr, nstr, fix)
+    # the format of the kernel's own argument table (the scratch pointer: a lattice whose adjoint takes a second pass)
+    kernel = which + ('_fix' if fix else '')
+    fmt, om_i = K.arg_format(kernel, idx), [a.kind for a in K.table(kernel)].index('rate')
     code = 'i' if idx == 'int' else 'q'
     om_c = 'f' if dtype == 'float32' else 'd'
     assert fmt == 'Q' * nptr + 'iii' + code * nstr + 'q' * ntens + om_c + ('Qi' if fix else '')
@@ -251,29 +265,22 @@ def test_plan_argument_buffer_matches_struct(idx, dtype, which, force, scratch, 
 @pytest.mark.parametrize('idx', ['int', 'long long'])
 @pytest.mark.parametrize('programs', [False, True])
 def test_rho_plan_argument_buffer_matches_struct(idx, programs, monkeypatch):
-    """``rho_plan()``'s ``fmt``, with and without the src / ids slots of inline link programs (``extra``): layout as
-    the C struct; the launch patches the three leading pointers and the two ``extra`` pointers only."""
+    """``rho_plan()``'s ``fmt`` is what ``lbm_adj_rho`` declares, with and without link programs on the lattice (on
+    the HIP target they run in the fix-up kernel: the second pass takes no src / ids slots): layout as the C struct;
+    the launch patches the three leading pointers only."""
     from pystencils_autodiff_amd.backends import hip_runtime as rt
-    K = _plain_kernels('float64')
-    if programs:
-        K.programs = ((None,) * 9,)                      # (only its presence is read here)
-    fmt, extra_i = K._rho_format(idx)
+    K = _rho_kernels('float64', programs)
+    fmt = K.arg_format('adj_rho', idx)
     code = 'i' if idx == 'int' else 'q'
-    assert fmt == 'QQQiii' + code * 4 + ('QQ' + code * 4 if programs else '')
-    assert extra_i == (10 if programs else None)
+    assert fmt == 'QQQiii' + code * 4
+    assert [a.name for a in K.table('adj_rho')][:3] == ['out', 'nbmask', 'rho_adj']
     vals = _values(fmt)
     S, packed = _check_layout(fmt, vals)
     sent = []
     monkeypatch.setattr(rt, 'launch', lambda fn, grid, block, args, stream, shared_bytes=0: sent.append(args))
     plan = LK.LaunchPlan(1, 3, packed, 3, None, None, None)
     patched = {0: 0xB1B1B1B1B1B1B1B1, 1: 0xB2B2B2B2B2B2B2B2, 2: 0xB3B3B3B3B3B3B3B3}
-    extra = None
-    if programs:
-        plan.extra = LK._offset(fmt, extra_i)
-        assert plan.extra == getattr(S, 'a10').offset
-        extra = (0xC1C1C1C1C1C1C1C1, 0xC2C2C2C2C2C2C2C2)
-        patched.update({10: extra[0], 11: extra[1]})
-    plan(tuple(patched[k] for k in range(3)), 5, extra=extra)
+    plan(tuple(patched[k] for k in range(3)), 5)
     got = S.from_buffer_copy(sent[0])
     for i, v in enumerate(vals):
         assert getattr(got, f'a{i}') == patched.get(i, v)

@@ -272,7 +272,7 @@ def test_fp16_argument_format_and_mode():
     from pystencils_autodiff_amd.lbm._lattice_kernels import LatticeKernels
     from tests.test_lbm_addressing import I31, _meta
     K = LatticeKernels(lbm.LBStencil('D2Q9'), True, np.float16, False, 'gpu')
-    fmt, om_i = K._arg_format('int', 2, 4, 8)
+    fmt, om_i = K.arg_format('fwd', 'int'), [a.kind for a in K.table('fwd')].index('rate')
     assert fmt[om_i] == 'f' and fmt == 'QQQQ' + 'iii' + 'i' * 8 + 'qq' + 'f'
     assert K._mode([_meta(I31 // 2 - 1, 'float16')]) == ('int', 'buf')
     assert K._mode([_meta(I31 // 2, 'float16')]) == ('int', 'ptr')

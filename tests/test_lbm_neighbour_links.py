@@ -570,6 +570,47 @@ def test_all_lattice_sources_unchanged():
     assert [k for k in golden if shas[k] != golden[k]] == []
 
 
+def _declared_formats(source):
+    """kernel name → the ``struct`` codes of its parameter list, parsed out of the emitted HIP text: a pointer is
+    ``Q``, ``const int`` ``i``, ``const IDX`` ``i`` / ``q`` by the typedef, ``const long long`` ``q``, ``const float`` /
+    ``const double`` ``f`` / ``d``."""
+    import re
+    idx = re.search(r'^typedef (.+) IDX;$', source, re.M).group(1)
+    scalar = {'const int': 'i', 'const IDX': {'int': 'i', 'long long': 'q'}[idx], 'const long long': 'q',
+              'const float': 'f', 'const double': 'd'}
+    out = {}
+    for name, params in re.findall(r'^extern "C" __global__ void __launch_bounds__\(\d+\) (\w+)\(([^)]*)\)$', source,
+                                   re.M):
+        out[name] = ''.join('Q' if '*' in p else scalar[p.strip().rsplit(' ', 1)[0]] for p in params.split(','))
+    return out
+
+
+def test_launch_formats_match_the_emitted_signatures():
+    """The launcher's argument-buffer format of every kernel (``LatticeKernels.arg_format``) is the parameter list the
+    printer emits for it: every lattice of ``_all_lattices`` plus a float16, an ω-field, a force-field and a Smagorinsky
+    lattice, both index types, ``lbm_fwd`` / ``lbm_adj`` / ``lbm_adj_rho`` (lattices with a second pass on the HIP
+    target) / ``lbm_adj_fix`` (lattices with link programs). Nothing is compiled."""
+    from pystencils_autodiff_amd.lbm._lattice_kernels import LatticeKernels
+    st = lbm.LBStencil('D3Q19')
+    lattices = {name: build('gpu') for name, build in _all_lattices().items()}
+    lattices['float16'] = LatticeKernels(st, True, np.float16, True, 'gpu', zero_centered=True)
+    lattices['omega-field'] = LatticeKernels(st, True, np.float32, False, 'gpu', omega_field=True)
+    lattices['force-field'] = LatticeKernels(st, False, np.float64, True, 'gpu', force_model='guo', force_field=True)
+    lattices['smagorinsky'] = LatticeKernels(lbm.LBStencil('D2Q9'), True, np.float64, True, 'gpu', smagorinsky=0.12,
+                                             omega_field=True)
+    seen = set()
+    for name, K in lattices.items():
+        for idx, addr in (('int', 'buf'), ('long long', 'ptr')):
+            main = _declared_formats(K.source(idx, addr))
+            assert sorted(main) == ['lbm_adj'] + ['lbm_adj_rho'] * bool(K.rho_links) + ['lbm_fwd'], name
+            fix = _declared_formats(K.source(idx, addr, fix=True)) if K.programs is not None else {}
+            assert sorted(fix) == ['lbm_adj_fix'] * (K.programs is not None), name
+            for kernel, fmt in {**main, **fix}.items():
+                assert K.arg_format(kernel[len('lbm_'):], idx) == fmt, (name, idx, kernel)
+                seen.add(kernel)
+    assert seen == {'lbm_fwd', 'lbm_adj', 'lbm_adj_rho', 'lbm_adj_fix'}
+
+
 # --- HIP kernels -----------------------------------------------------------------------------------------------
 GPU_CASES = [('slip', 'D2Q9', (70, 33), 'float64', 'srt', True),      # x no multiple of 64, the tangential read wraps
              ('box', 'D2Q9', (64, 40), 'float32', 'trt', False),      # the corner fallback

@@ -256,7 +256,7 @@ def test_other_omega_expressions_take_the_autodiffop_schedule(what):
 @pytest.mark.parametrize('method', ['srt', 'trt-magic', 'trt-rate', 'mrt'])
 def test_domega_formulas_match_the_symbolic_rule(method, guo):
     """``∂dst_i/∂ω`` by ``sp.diff`` of the D2Q9 rule (subexpressions inlined) against the formulas of
-    ``_lattice_source._Printer.omega_adjoint``: SRT ``−n_i``; TRT ``−(a′ n_i + b′ n_ī)``; MRT ``−(P_ω n)_i``; Guo adds
+    ``_lattice_source.omega.omega_adjoint``: SRT ``−n_i``; TRT ``−(a′ n_i + b′ n_ī)``; MRT ``−(P_ω n)_i``; Guo adds
     ``−½ w_i T_i`` — evaluated at a random state (exact rationals)."""
     from pystencils_autodiff_amd.lbm._method import mrt_relaxation_matrices
     st = lbm.LBStencil('D2Q9')

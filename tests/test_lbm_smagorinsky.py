@@ -4,7 +4,7 @@
     N = √(2 Σ_ab Π_ab²),   Π_ab = Σ_i c_ia c_ib (f_i − feq_i)
 
 of the cell's own pulled pdfs; the lattice kernels evaluate it in the forward and the adjoint cell and carry its chain
-factors (``_lattice_source._Printer.smagorinsky_adjoint``).
+factors (``_lattice_source.smagorinsky.smagorinsky_adjoint``).
 
 Reference: ``oracle/lbm.py``'s streaming and ``collide`` with the per-cell tensor ω_eff(fs) computed HERE from the formulas
 above (``OL.equilibrium``), in torch float64, and ``torch.autograd.grad`` through T = 3 steps. Every parity test asserts on
