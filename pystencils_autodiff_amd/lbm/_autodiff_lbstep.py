@@ -59,32 +59,46 @@ class SimulationResultsTensors:
         self.output_velocity_tensor = output_velocity_tensor
 
 
-def _lattice_sweeps(step, which, launches, force=None, dforce=None, omf=None, domf=None):
+def _lattice_sweeps(step, which, launches, force=None, dforce=None, omf=None, domf=None, macro=None):
     """The lattice kernels over ``launches`` (tensor tuples of ``LatticeKernels.forward`` / ``adjoint``) on the
     current stream: one launch plan per distinct (shapes, strides) — the first, middle and last steps — and only
     the pointers packed per launch. ``force`` (a per-cell force field): bound to every launch; ``dforce``: the
     adjoint launches add their force adjoints into it. ``omf`` / ``domf``: the per-cell relaxation rate and its
-    adjoint, likewise."""
+    adjoint, likewise. ``macro``: per launch None, or the density / velocity arrays of an observed step by name
+    (``LatticeKernels.operands``) — those launches run the kernels' density / velocity variant, the others the plain
+    kernels with no argument more."""
     K = step._lattice_kernels()
     mask = step._flag_arg()
     ids = step._ids_arg()
     cells = step._cells_arg()
     om = step._omega_of()
-    stream = _torch()._C._cuda_getCurrentRawStream(launches[0][0].device.index)
-    rho = K.rho_buffer(launches[0][0]) if which == 'adj' and K.link_pass else None
     if which != 'adj':
         dforce = domf = None
-    # once: the launches differ in their pdf arrays only (the leading pointer slots)
+    macro = macro or [None] * len(launches)
+    if not step._gpu:
+        # the C kernels on numpy arrays (both adjoint passes in one call)
+        for ts, m in zip(launches, macro):
+            if which == 'adj':
+                K.adjoint(*ts, om, mask, ids=ids, force=force, dforce=dforce, omf=omf, domf=domf, **(m or {}))
+            else:
+                K.forward(*ts, om, mask, ids=ids, force=force, omf=omf, **(m or {}))
+        return
+    stream = _torch()._C._cuda_getCurrentRawStream(launches[0][0].device.index)
+    rho = K.rho_buffer(launches[0][0]) if which == 'adj' and K.link_pass else None
+    # once: the launches differ in their pdf arrays (the leading pointer slots) and, the observed ones, in the
+    # density / velocity arrays (the trailing ones)
     mptr = K.pointers(which, K.operands((), mask, ids, force, dforce, omf, domf, rho))[len(launches[0]):]
+    mnames = K.table_pointer_names(which, True)[len(launches[0]) + len(mptr):]
     plans = {}
-    for ts in launches:
-        sig = tuple(t.stride() for t in ts)
+    for ts, m in zip(launches, macro):
+        sig = tuple(t.stride() for t in ts) + (m is not None,)
         plan = plans.get(sig)
         if plan is None:
-            plan = plans[sig] = K.plan(which, list(ts), mask, om, ids, force, dforce, omf=omf, domf=domf)
-        plan(tuple(t.data_ptr() for t in ts) + mptr, stream, om)
+            plan = plans[sig] = K.plan(which, list(ts), mask, om, ids, force, dforce, omf=omf, domf=domf, macro=m)
+        plan(tuple(t.data_ptr() for t in ts) + mptr +
+             (tuple(0 if m.get(n) is None else m[n].data_ptr() for n in mnames) if m else ()), stream, om)
         # link-program walls (HIP): the fix-up kernels over the cells next to them
-        K.fix_launch(which, list(ts), mask, om, ids, force, dforce, cells, stream, omf, domf)
+        K.fix_launch(which, list(ts), mask, om, ids, force, dforce, cells, stream, omf, domf, m)
         if rho is not None:
             # the second pass of density-weighted walls (and, on the CPU, link programs) on this launch's output
             K.rho_pass(ts[2], mask, rho, stream)
@@ -661,11 +675,17 @@ class AutoDiffLatticeBoltzmannStep:
         self._records = self._records[:len(self._records) - int(time_steps)]
 
     # -- torch ops ---------------------------------------------------------------------------------
-    def create_timestep_op(self, num_time_steps, input_field_to_tensor_dict=None, backend='torch_native'):
+    def create_timestep_op(self, num_time_steps, input_field_to_tensor_dict=None, backend='torch_native',
+                           macroscopic_outputs=None):
         """A ``torch.autograd.Function`` for ``num_time_steps`` steps: ``Op.apply(pdfs)`` with the interior
         pdfs (``[*domain_size, q]``) returns the pdfs after the steps; its backward runs the adjoint steps
         in reverse over the recorded states (``_autodiff_lbstep.py:189-247``; the reference's
-        ``torch_native`` backend ignores the loops and differentiates one kernel launch)."""
+        ``torch_native`` backend ignores the loops and differentiates one kernel launch).
+
+        ``macroscopic_outputs``: ``True`` or an int ``k ≥ 1`` — the op returns ``(pdfs, rho, vel)`` with the density
+        ``rho [n, *domain]`` and the velocity ``vel [n, *domain, D]`` of the states k, 2k, …, nk, ``n = T // k``
+        (state t: the output of step t), written by the lattice kernels that compute those states, and its backward
+        takes their gradients too (``_observed_timestep_op``)."""
         if str(backend).lower() not in ('torch_native', 'torch'):
             raise NotImplementedError(f"backend '{backend}': only the torch backends are built")
         extras = list(self._additional_fields)
@@ -673,6 +693,8 @@ class AutoDiffLatticeBoltzmannStep:
         unknown = [getattr(f, 'name', f) for f in (input_field_to_tensor_dict or {}) if getattr(f, 'name', f) not in known]
         if unknown:
             raise ValueError(f'input fields {unknown} are not read by the update rule (inputs: {sorted(known)})')
+        if macroscopic_outputs is not None and macroscopic_outputs is not False:
+            return self._observed_timestep_op(int(num_time_steps), macroscopic_outputs, extras)
         torch = _torch()
         step = self
         T = int(num_time_steps)
@@ -777,6 +799,128 @@ class AutoDiffLatticeBoltzmannStep:
         LbmTimesteps.lb_step = self
         return LbmTimesteps
 
+    def _observed_timestep_op(self, T, every, extras):
+        """The time-step op that also returns the density and the velocity of every ``every``-th state
+        (``create_timestep_op(macroscopic_outputs=…)``): ``Op.apply(pdfs, *extras)`` → ``(pdfs, rho, vel)``.
+
+        The launches of the observed steps run the lattice kernels' density / velocity variant — the forward cell
+        stores ρ and u of the state it writes (the compute type: float32 for float16 pdfs; 0 in obstacle cells), the
+        adjoint cell adds the seeds to ``g`` where it loads it — and every other launch the plain kernels.
+        ``rho [n, *domain]`` and ``vel [n, *domain, D]`` (stored component-first, a permuted view) are one
+        uninitialised allocation each. Backward takes ``(grad_pdfs, grad_rho, grad_vel)``, any of them None (both
+        observable gradients None: the plain adjoint kernels throughout); an observable's gradient in the layout the
+        op returned is read in place, any other gets one copy."""
+        if self._lattice is None:
+            raise NotImplementedError(
+                'macroscopic_outputs: the density / velocity outputs are written by the lattice kernels, and this '
+                'rule is not on the lattice schedule (it runs on the AutoDiffOp kernels: a rule not made by '
+                'create_lb_update_rule, time-constant or other additional fields, a symbolic rate or force the '
+                'lattice kernels do not take, or PSAD_LBM_LATTICE=0)')
+        if isinstance(every, float) or int(every) < 1:
+            raise ValueError(f'macroscopic_outputs: True or an int k >= 1, got {every!r}')
+        torch = _torch()
+        step, k, gpu = self, int(every), self._gpu
+        n, D, dims = T // k, len(self.domain_size), list(self.domain_size)
+        slot = {j * k - 1: j - 1 for j in range(1, n + 1)}          # launch t (its output: state t + 1) → slot
+        pdt = np.dtype(self.pdf_field.dtype.numpy_dtype)
+        cdt = getattr(torch, 'float64' if pdt == np.float64 else 'float32')     # the kernels' compute type
+        view = (0,) + tuple(range(2, D + 2)) + (1,)                 # [n, D, *domain] → [n, *domain, D]
+
+        def arrays(t):
+            """What the kernels take: the tensor itself, on the C target its memory as a numpy array."""
+            return t if gpu else t.numpy()
+
+        def as_returned(g, like):
+            """The gradient ``g`` of an output ``like``: itself if it has that layout, else one copy in it."""
+            if g is None:
+                return torch.zeros_like(like)           # (preserves the strides: dense, non-overlapping)
+            g = g.detach()
+            if g.dtype == like.dtype and g.device == like.device and tuple(g.shape) == tuple(like.shape) and \
+                    tuple(g.stride()) == tuple(like.stride()):
+                return g
+            out = torch.empty_like(like)
+            out.copy_(g)
+            return out
+
+        class LbmTimestepsObserved(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, pdfs, *xs):
+                if len(xs) != len(extras):
+                    raise TypeError(f'{LbmTimestepsObserved.__name__}.apply(pdfs, {", ".join(f.name for f in extras)}): '
+                                    f'{1 + len(xs)} tensors given')
+                ex = {f.name: step._field_layout(f, x.detach()) for f, x in zip(extras, xs)}
+                if not gpu:
+                    ex = {name: x.cpu().numpy() for name, x in ex.items()}
+                ctx.extras = ex
+                x0 = pdfs.detach()
+                if gpu:
+                    x0 = x0 if step._lattice_input_ok(x0) else step._as_layout(x0)
+                    states = [x0] + step._internal_states(T - 1) + [step._alloc(zero=False)]
+                    dev = x0.device
+                else:
+                    states = [np.asarray(x0.cpu().numpy(), dtype=pdt)] + [step._alloc(zero=False) for _ in range(T)]
+                    dev = 'cpu'
+                rho = torch.empty([n] + dims, dtype=cdt, device=dev)
+                vel = torch.empty([n, D] + dims, dtype=cdt, device=dev).permute(*view)
+                macro = [None] * T
+                for t, j in slot.items():
+                    macro[t] = dict(rho_out=arrays(rho[j]), vel_out=arrays(vel[j]))
+                _lattice_sweeps(step, 'fwd', [(states[t], states[t + 1]) for t in range(T)], step._force_arg(ex),
+                                omf=step._omega_arg(ex), macro=macro)
+                ctx.input_is_state0 = gpu and states[0].data_ptr() == pdfs.data_ptr()
+                ctx.records = states[1:-1] if ctx.input_is_state0 else states[:-1]
+                out = states[-1] if gpu else torch.from_numpy(states[-1])
+                # (the outputs are what a compressible rule's adjoint reads: saved, so that an in-place change between
+                # forward and backward raises)
+                ctx.save_for_backward(pdfs if ctx.input_is_state0 else None, rho, vel)
+                ctx.set_materialize_grads(False)
+                return out, rho, vel
+
+            @staticmethod
+            def backward(ctx, grad, grad_rho, grad_vel):
+                ex = ctx.extras
+                ctx.extras = None
+                x0, rho, vel = ctx.saved_tensors
+                rho, vel = rho.detach(), vel.detach()
+                if grad is None:
+                    g = step._alloc(zero=True)
+                elif gpu:
+                    g = grad if step._lattice_input_ok(grad) else step._as_layout(grad)
+                else:
+                    g = np.asarray(grad.detach().cpu().numpy(), dtype=pdt)
+                records = list(ctx.records)
+                if ctx.input_is_state0:
+                    x0 = x0.detach()
+                    records = [x0 if step._lattice_input_ok(x0) else step._as_layout(x0)] + records
+                ctx.records = None
+                ping = step._internal_states(min(2, T - 1)) if gpu else \
+                    [step._alloc(zero=False) for _ in range(min(2, T - 1))]
+                out = step._alloc(zero=False)
+                cur, launches, macro = g, [], []
+                seeded = grad_rho is not None or grad_vel is not None
+                if seeded:
+                    drho, dvel = as_returned(grad_rho, rho), as_returned(grad_vel, vel)
+                for t in reversed(range(T)):
+                    nxt = out if t == 0 else ping[(T - 1 - t) % 2]
+                    launches.append((records[t], cur, nxt))
+                    j = slot.get(t) if seeded else None
+                    macro.append(None if j is None else dict(rho_out=arrays(rho[j]), vel_out=arrays(vel[j]),
+                                                             drho=arrays(drho[j]), dvel=arrays(dvel[j])))
+                    cur = nxt
+                # the force / ω adjoint: every step's adjoint launch adds its share into one array, zeroed once
+                F, W = step._force_arg(ex), step._omega_arg(ex)
+                dex = {f.name: (torch.zeros_like if gpu else np.zeros_like)(ex[f.name]) for f in extras}
+                _lattice_sweeps(step, 'adj', launches, F, None if F is None else dex[step._force_field.name],
+                                W, None if W is None else dex[step._omega_field.name], macro=macro)
+                if not gpu:
+                    return (torch.from_numpy(out), *[torch.from_numpy(dex[f.name]) for f in extras])
+                return (out, *[dex[f.name] for f in extras])
+
+        LbmTimestepsObserved.num_time_steps = T
+        LbmTimestepsObserved.lb_step = self
+        LbmTimestepsObserved.observed_states = tuple(j * k for j in range(1, n + 1))
+        return LbmTimestepsObserved
+
     def _field_layout(self, f, t):
         """An additional input tensor in field ``f``'s memory layout (fzyx: components-first) on the step's side."""
         if not self._gpu:
@@ -794,11 +938,13 @@ class AutoDiffLatticeBoltzmannStep:
 
     def create_end_to_end_op(self, num_time_steps, velocity_input_tensor, density_input_tensor,
                              additional_fields_to_tensor_map=None, force_input_tensor=None, backend='torch_native',
-                             num_times_steps_without_save=0, **kernel_compilation_kwargs):
+                             num_times_steps_without_save=0, macroscopic_outputs=False, **kernel_compilation_kwargs):
         """Equilibrium from (ρ, u) → ``num_time_steps`` steps → (ρ, u), differentiable end to end
         (``_autodiff_lbstep.py:310-334``, there TensorFlow only): the setter op, the time-step ops in groups of
         ``num_times_steps_without_save + 1`` steps, the getter op, evaluated on the given tensors (torch
-        autograd records the chain). Returns ``SimulationResultsTensors``."""
+        autograd records the chain). Returns ``SimulationResultsTensors``. ``macroscopic_outputs``: every group is
+        observed at its end (``create_timestep_op(group, macroscopic_outputs=group)``) and the result also carries
+        ``density_trajectory`` ``[groups, *domain]`` and ``velocity_trajectory`` ``[groups, *domain, D]``."""
         if str(backend).lower() not in ('torch_native', 'torch'):
             raise NotImplementedError(f"backend '{backend}': only the torch backends are built")
         from ._method import force_is_field
@@ -820,13 +966,24 @@ class AutoDiffLatticeBoltzmannStep:
                              'getter': self.create_macroscopic_getter_op(backend, **kernel_compilation_kwargs)}
         ops = self._e2e_ops
         group = int(num_times_steps_without_save) + 1
-        step_op = self.create_timestep_op(group, backend=backend)
+        step_op = self.create_timestep_op(group, backend=backend,
+                                          macroscopic_outputs=group if macroscopic_outputs else None)
         (input_pdf,) = ops['setter'].apply(density_input_tensor, velocity_input_tensor)
         out = input_pdf
+        trajectory = []
         for _ in range(int(num_time_steps) // group):
-            out = step_op.apply(out, *xs)
+            if macroscopic_outputs:
+                out, *observed = step_op.apply(out, *xs)
+                trajectory.append(observed)
+            else:
+                out = step_op.apply(out, *xs)
         rho, vel = self._apply_getter(ops['getter'], out, given)
-        return SimulationResultsTensors(input_pdf, out, rho, vel)
+        result = SimulationResultsTensors(input_pdf, out, rho, vel)
+        if macroscopic_outputs:
+            torch = _torch()
+            result.density_trajectory = torch.cat([r for r, _ in trajectory]) if trajectory else None
+            result.velocity_trajectory = torch.cat([v for _, v in trajectory]) if trajectory else None
+        return result
 
     def _macroscopic_fields(self):
         dt = self.pdf_field.dtype.numpy_dtype

@@ -113,6 +113,13 @@ def _stride_values(ops, D):
     if ops.get('omf') is not None:
         sw = _element_strides(ops['omf'])
         v.update(zip(('w_z', 'w_y', 'w_x'), [0] * (3 - len(sw)) + sw))
+    # the density / velocity outputs and their seeds (one set of strides: the seeds have the outputs' layout)
+    rho = ops.get('rho_out') if ops.get('rho_out') is not None else ops.get('drho')
+    vel = ops.get('vel_out') if ops.get('vel_out') is not None else ops.get('dvel')
+    if rho is not None:
+        sr = _element_strides(rho)
+        v.update(zip(('r_z', 'r_y', 'r_x'), [0] * (3 - len(sr)) + sr))
+        v.update(zip(('v_c', 'v_z', 'v_y', 'v_x'), lattice_strides(vel, D)))
     return v
 
 
@@ -177,44 +184,54 @@ class LatticeKernels:
         # mode), and the names of the pointers among them, which a launch patches (``lbm_adj_fix``: ``lbm_adj``'s)
         self._tables = {k: kernel_args(self._spec(fix=k == 'adj_fix'), k) for k in KERNELS}
         self._ptr_names = {k: tuple(a.name for a in t if a.kind == POINTER) for k, t in self._tables.items()}
+        # ... and of the variant with the density / velocity outputs (``macro``: a module of its own, launched for
+        # the observed steps only)
+        self._mtables = {k: kernel_args(self._spec(fix=k == 'adj_fix', macro=True), k) for k in KERNELS}
+        self._mptr_names = {k: tuple(a.name for a in t if a.kind == POINTER) for k, t in self._mtables.items()}
 
-    def _spec(self, idx='int', addr='buf', fix=False):
+    def _spec(self, idx='int', addr='buf', fix=False, macro=False):
         """What ``source`` prints: the C spec (inline link programs), or of a HIP module: the main kernels, or
-        (``fix``) the fix-up kernels of the cells next to link-program walls."""
+        (``fix``) the fix-up kernels of the cells next to link-program walls. ``macro``: the variant that writes ρ
+        and u of the stored state and takes their adjoint seeds (``LatticeSource.macroscopic``)."""
         if self.target != 'gpu':
-            return self.spec
+            return dataclasses.replace(self.spec, macroscopic=True) if macro else self.spec
         mode = 'fix' if fix else 'main' if self.programs is not None else 'inline'
-        return dataclasses.replace(self.spec, idx=idx, addr=addr, mode=mode)
+        return dataclasses.replace(self.spec, idx=idx, addr=addr, mode=mode, macroscopic=bool(macro))
 
-    def source(self, idx='int', addr='buf', fix=False):
-        return emit(self._spec(idx, addr, fix))
+    def source(self, idx='int', addr='buf', fix=False, macro=False):
+        return emit(self._spec(idx, addr, fix, macro))
 
-    def table(self, kernel):
+    def table(self, kernel, macro=False):
         """The arguments of ``lbm_{kernel}`` ('fwd' / 'adj' / 'adj_rho' / 'adj_fix')."""
-        return self._tables[kernel]
+        return (self._mtables if macro else self._tables)[kernel]
+
+    def table_pointer_names(self, kernel, macro=False):
+        """The names of the pointer arguments of ``lbm_{kernel}``, in the table's order (``lbm_adj_fix``: ``lbm_adj``'s
+        and the cell list)."""
+        return (self._mptr_names if macro else self._ptr_names)[kernel]
 
     def arg_format(self, kernel, idx):
         """The ``struct`` codes of ``lbm_{kernel}``'s argument buffer (``_pack``) with strides of type ``idx``."""
         return struct_format(self.table(kernel), idx, self.ct)
 
     # -- GPU ---------------------------------------------------------------------------------------
-    def _gpu_fn(self, which, idx, addr, device):
-        key = (which, idx, addr, device)
+    def _gpu_fn(self, which, idx, addr, device, macro=False):
+        key = (which, idx, addr, device) + (('macro',) if macro else ())
         fn = self._fns.get(key)
         if fn is None:
             from ..backends import hip_runtime as rt
-            code = rt.compile_hip(self.source(idx, addr, fix=which.endswith('fix')), name='psad_lbm.hip')
+            code = rt.compile_hip(self.source(idx, addr, fix=which.endswith('fix'), macro=macro), name='psad_lbm.hip')
             fn = self._fns[key] = rt.load_function(code, f'lbm_{which}', device)
         return fn
 
-    def build(self):
+    def build(self, macro=False):
         from ..backends import hip_runtime as rt
         if self.target == 'gpu':
             # both addressing modes of small arrays, and what arrays of 2³¹ − 1 elements and more take
-            return [rt.compile_hip(self.source(i, a, f), name='psad_lbm.hip')
+            return [rt.compile_hip(self.source(i, a, f, macro), name='psad_lbm.hip')
                     for i, a in (('int', 'buf'), ('int', 'ptr'), ('long long', 'ptr'))
                     for f in ((False, True) if self.programs is not None else (False,))]
-        return self._cpu_fn('fwd')
+        return self._cpu_fn('fwd', macro)
 
     def _check_domain(self, arrays, mask, ids, ok=lambda a, itemsize: True):
         """What the kernels of both targets need: pdf arrays ``[*domain, Q]`` of one shape, the neighbour mask with
@@ -244,16 +261,38 @@ class LatticeKernels:
             raise ValueError('the periodic lattice needs at least 2 cells per axis')
 
     @staticmethod
-    def operands(tensors, mask, ids, force=None, dforce=None, omf=None, domf=None, scratch=None):
+    def operands(tensors, mask, ids, force=None, dforce=None, omf=None, domf=None, scratch=None, macro=None):
         """Argument name → operand (torch tensors, or numpy arrays on the C path; None: not given) of ``lbm_fwd``
-        (``tensors``: src, dst) or ``lbm_adj`` / ``lbm_adj_fix`` (src, g, out)."""
+        (``tensors``: src, dst) or ``lbm_adj`` / ``lbm_adj_fix`` (src, g, out). ``macro``: None, or by name the arrays
+        of the density / velocity variant (``rho_out``, ``vel_out``, ``drho``, ``dvel``)."""
         return dict(zip(('src', 'dst') if len(tensors) == 2 else ('src', 'g', 'out'), tensors), nbmask=mask,
-                    wallid=ids, force=force, dforce=dforce, omf=omf, domega=domf, rho_adj=scratch)
+                    wallid=ids, force=force, dforce=dforce, omf=omf, domega=domf, rho_adj=scratch, **(macro or {}))
 
-    def pointers(self, kernel, ops):
+    def pointers(self, kernel, ops, macro=False):
         """The pointer slots a launch of ``lbm_{kernel}`` patches, in the table's order, from the operands ``ops``
         (0 for one not given)."""
-        return tuple(_ptr(ops.get(n)) for n in self._ptr_names[kernel])
+        return tuple(_ptr(ops.get(n)) for n in (self._mptr_names if macro else self._ptr_names)[kernel])
+
+    def _macro_check(self, which, shape, macro, xp_tensor=True):
+        """The arrays of the density / velocity variant, by name: the forward's ``rho_out`` ``[*domain]`` and ``vel_out``
+        ``[*domain, D]``, the adjoint's seeds ``drho`` / ``dvel`` (and, compressible, the recorded outputs, with the
+        seeds' strides), all of the compute type; returns them in the table's order."""
+        D = self.stencil.D
+        names = [a.name for a in self._mtables[which] if a.group == 'macro' and a.kind == POINTER]
+        dt = 'float64' if self.ct == 'double' else 'float32'
+        for n in names:
+            t = macro.get(n)
+            if t is None:
+                raise ValueError(f'the density / velocity lattice kernels need {", ".join(names)}: {n} is missing')
+            want = tuple(shape[:D]) + ((D,) if n in ('vel_out', 'dvel') else ())
+            if tuple(t.shape) != want:
+                raise ValueError(f'{n} of shape {tuple(t.shape)}: expected {want}')
+            if str(t.dtype).split('.')[-1] != dt:
+                raise ValueError(f'{n} dtype {t.dtype}: expected {dt}')
+        st = [tuple(macro[n].stride() if xp_tensor else macro[n].strides) for n in names]
+        if which == 'adj' and len(names) == 4 and (st[0] != st[2] or st[1] != st[3]):
+            raise ValueError('the density / velocity seeds must have the strides of the recorded outputs')
+        return [macro[n] for n in names]
 
     def _values(self, table, ops, omega=None):
         """The value of every argument of ``table`` from the operands ``ops`` (a pointer not given: 0, a slot patched
@@ -290,11 +329,11 @@ class LatticeKernels:
             addr = 'ptr'
         return idx, addr
 
-    def _launch_mode(self, tensors, force=None, dforce=None, omf=None, domf=None):
+    def _launch_mode(self, tensors, force=None, dforce=None, omf=None, domf=None, *more):
         """``(idx, addr)`` of a ``plan()`` launch: ``_mode`` of the pdf tensors; the force and the ω field (and
         their adjoints) are read through plain pointers with IDX offsets, so a far-reaching one widens ``idx`` alone."""
         idx, addr = self._mode(tensors)
-        if max([self._reach(t) for t in (force, dforce, omf, domf) if t is not None], default=0) >= 2 ** 31 - 1:
+        if max([self._reach(t) for t in (force, dforce, omf, domf) + more if t is not None], default=0) >= 2 ** 31 - 1:
             idx = 'long long'
         return idx, addr
 
@@ -324,52 +363,64 @@ class LatticeKernels:
                 tuple(field.stride() if xp_tensor else field.strides):
             raise ValueError(f'the {short} adjoint must have the strides of the {name}')
 
-    def plan(self, which, tensors, mask, omega, ids=None, force=None, dforce=None, fix=None, omf=None, domf=None):
+    def plan(self, which, tensors, mask, omega, ids=None, force=None, dforce=None, fix=None, omf=None, domf=None,
+             macro=None):
         """The launch of ``which`` ('fwd' / 'adj') on tensors of these shapes, strides, dtype and device (with or
         without walls): a ``LaunchPlan`` whose pointer slots and relaxation rate are patched per launch — the
         time-step op launches T of them per apply. ω is not part of the key (a trained or scheduled rate reuses the
         plan); the plan is built with the first ω it sees. ``fix``: (cells,) — the fix-up kernel of ``which`` over
-        the listed cells (int32 cell indices)."""
+        the listed cells (int32 cell indices). ``macro``: the arrays of the density / velocity variant (``operands``),
+        whose pointers every launch patches too."""
         key = (which, mask is not None) + tuple((tuple(t.shape), tuple(t.stride()), t.dtype, t.device)
                                                 for t in tensors) + \
             ((tuple(force.shape), tuple(force.stride())) if force is not None else ()) + \
             (('omf', tuple(omf.shape), tuple(omf.stride())) if omf is not None else ()) + \
-            ((fix[0].data_ptr(), int(fix[0].numel())) if fix is not None else ())
+            ((fix[0].data_ptr(), int(fix[0].numel())) if fix is not None else ()) + \
+            (('macro',) + tuple((n, tuple(t.stride())) for n, t in sorted(macro.items()) if t is not None)
+             if macro else ())
         plan = self._plans.get(key)
         if plan is not None:
             return plan
+        marr = self._macro_check(which, tuple(tensors[0].shape), macro) if macro else []
+        if any(not t.is_cuda or t.device != tensors[0].device for t in marr):
+            raise ValueError('the density / velocity arrays must be on the pdf tensors\' device')
         self._field_check('force', tuple(tensors[0].shape), force, dforce, which)
         self._field_check('omega', tuple(tensors[0].shape), omf, domf, which)
         self._check(tensors, mask, ids)
         if any(t is not None and (not t.is_cuda or t.device != tensors[0].device) for t in (omf, domf)):
             raise ValueError('the relaxation-rate field must be on the pdf tensors\' device')
-        idx, addr = self._launch_mode(tensors, force, dforce, omf, domf)
+        idx, addr = self._launch_mode(tensors, force, dforce, omf, domf, *marr)
         dev = tensors[0].device.index
         # (the fix-up kernel: the cell list and its length after the main kernel's arguments)
         kernel = which + ('_fix' if fix is not None else '')
-        fn = self._gpu_fn(kernel, idx, addr, dev)
+        fn = self._gpu_fn(kernel, idx, addr, dev, bool(macro))
         Z, Y, X = self._extent(tensors[0])
         nblocks = self._blocks(X, Y, Z) if fix is None else -(-int(fix[0].numel()) // FIX_BLOCK)
-        table = self.table(kernel)
+        table = self.table(kernel, bool(macro))
         fmt = struct_format(table, idx, self.ct)
-        ops = dict(self.operands(tensors, mask, ids, force, dforce, omf, domf), cells=fix[0] if fix else None)
+        ops = dict(self.operands(tensors, mask, ids, force, dforce, omf, domf, macro=macro),
+                   cells=fix[0] if fix else None)
         om_i = [a.kind for a in table].index(RATE)
+        nptr = len((self._mptr_names if macro else self._ptr_names)[which])
         plan = self._plans[key] = LaunchPlan(fn, nblocks, _pack(fmt, *self._values(table, ops, omega)),
-                                             len(self._ptr_names[which]), dev, _offset(fmt, om_i), fmt[om_i])
+                                             nptr, dev, _offset(fmt, om_i), fmt[om_i])
         if fix is not None:
             plan.block = FIX_BLOCK
         return plan
 
-    def fix_launch(self, which, tensors, mask, omega, ids, force, dforce, cells, stream, omf=None, domf=None):
+    def fix_launch(self, which, tensors, mask, omega, ids, force, dforce, cells, stream, omf=None, domf=None,
+                   macro=None):
         """The fix-up launch after a main adjoint launch on ``tensors`` (HIP with link programs; nothing for the
         forward, which runs them inline, or when no cell is listed): the listed cells' adjoint with their programs'
         Jacobian terms, added atomically into the entries the main launch left zeroed (no second fix-up launch)."""
         if which != 'adj' or self.programs is None or self.target != 'gpu' or cells is None or \
                 int(cells.numel()) == 0:
             return
-        plan = self.plan(which, tensors, mask, omega, ids, force, dforce, fix=(cells,), omf=omf, domf=domf)
+        plan = self.plan(which, tensors, mask, omega, ids, force, dforce, fix=(cells,), omf=omf, domf=domf,
+                         macro=macro)
         rho = self.rho_buffer(tensors[0]) if self.link_pass else None
-        plan(self.pointers(which, self.operands(tensors, mask, ids, force, dforce, omf, domf, rho)), stream, omega)
+        plan(self.pointers(which, self.operands(tensors, mask, ids, force, dforce, omf, domf, rho, macro),
+                           bool(macro)), stream, omega)
 
     def _scratch_shape(self, domain):
         """Of the second adjoint pass's scratch array: one value per cell (density-weighted links); with inline link
@@ -405,27 +456,36 @@ class LatticeKernels:
                                              len(self._ptr_names['adj_rho']), dev, None, None)
         return plan
 
-    def forward(self, src, dst, omega, mask=None, stream=None, ids=None, force=None, cells=None, omf=None):
+    def forward(self, src, dst, omega, mask=None, stream=None, ids=None, force=None, cells=None, omf=None,
+                rho_out=None, vel_out=None):
         """``dst = stream-pull-collide(src)`` (torch tensors ``[*domain, q]``, any strides; ``force``: the per-cell
         force ``[*domain, D]`` of force-field kernels; ``omf``: the per-cell relaxation rate ``[*domain]`` of ω-field
-        kernels, which ignore ``omega``)."""
+        kernels, which ignore ``omega``). ``rho_out`` / ``vel_out`` (both or neither; the compute type, ``[*domain]``
+        and ``[*domain, D]``, any strides): also written, the density and the velocity of ``dst`` — 0 in obstacle
+        cells — by the kernels' density / velocity variant."""
+        macro = None if rho_out is None and vel_out is None else dict(rho_out=rho_out, vel_out=vel_out)
         if self.target != 'gpu':
-            return self._cpu('fwd', [src, dst], omega, mask, ids, force, omf=omf)
+            return self._cpu('fwd', [src, dst], omega, mask, ids, force, omf=omf, macro=macro)
         st = _stream(stream, src)
-        self.plan('fwd', [src, dst], mask, omega, ids, force, omf=omf)(
-            self.pointers('fwd', self.operands([src, dst], mask, ids, force, omf=omf)), st, omega)
+        self.plan('fwd', [src, dst], mask, omega, ids, force, omf=omf, macro=macro)(
+            self.pointers('fwd', self.operands([src, dst], mask, ids, force, omf=omf, macro=macro), bool(macro)),
+            st, omega)
 
     def adjoint(self, src, g, out, omega, mask=None, stream=None, ids=None, force=None, dforce=None, cells=None,
-                omf=None, domf=None):
+                omf=None, domf=None, rho_out=None, vel_out=None, drho=None, dvel=None):
         """``out = (∂ step / ∂ src)ᵀ g`` at the state ``src``; force-field kernels also ADD ``(∂ step / ∂ F)ᵀ g`` to
-        ``dforce``, ω-field kernels ``(∂ step / ∂ ω)ᵀ g`` to ``domf``."""
+        ``dforce``, ω-field kernels ``(∂ step / ∂ ω)ᵀ g`` to ``domf``. ``drho`` / ``dvel`` (both or neither): the
+        adjoint seeds of the density and the velocity of this step's output, added to ``g`` in the cell (with the
+        recorded ``rho_out`` / ``vel_out`` of that step, which a compressible rule reads)."""
+        macro = None if drho is None and dvel is None else dict(rho_out=rho_out, vel_out=vel_out, drho=drho, dvel=dvel)
         if self.target != 'gpu':
-            return self._cpu('adj', [src, g, out], omega, mask, ids, force, dforce, omf, domf)
+            return self._cpu('adj', [src, g, out], omega, mask, ids, force, dforce, omf, domf, macro)
         st = _stream(stream, src)
         rho = self.rho_buffer(src) if self.link_pass else None
-        self.plan('adj', [src, g, out], mask, omega, ids, force, dforce, omf=omf, domf=domf)(
-            self.pointers('adj', self.operands([src, g, out], mask, ids, force, dforce, omf, domf, rho)), st, omega)
-        self.fix_launch('adj', [src, g, out], mask, omega, ids, force, dforce, cells, st, omf, domf)
+        self.plan('adj', [src, g, out], mask, omega, ids, force, dforce, omf=omf, domf=domf, macro=macro)(
+            self.pointers('adj', self.operands([src, g, out], mask, ids, force, dforce, omf, domf, rho, macro),
+                          bool(macro)), st, omega)
+        self.fix_launch('adj', [src, g, out], mask, omega, ids, force, dforce, cells, st, omf, domf, macro)
         if rho is not None:
             self.rho_pass(out, mask, rho, st)
 
@@ -445,14 +505,15 @@ class LatticeKernels:
         return -(-(X * Y * Z) // 256)
 
     # -- CPU ---------------------------------------------------------------------------------------
-    def _cpu_fn(self, which):
-        fn = self._fns.get(which)
+    def _cpu_fn(self, which, macro=False):
+        key = (which, 'macro') if macro else which
+        fn = self._fns.get(key)
         if fn is None:
             from ..backends.cpu_kernel import compile_c
-            fn = self._fns[which] = compile_c(self.source(), f'lbm_{which}', openmp=True)
+            fn = self._fns[key] = compile_c(self.source(macro=macro), f'lbm_{which}', openmp=True)
         return fn
 
-    def _cpu(self, which, arrays, omega, mask, ids=None, force=None, dforce=None, omf=None, domf=None):
+    def _cpu(self, which, arrays, omega, mask, ids=None, force=None, dforce=None, omf=None, domf=None, macro=None):
         arrays = [np.asarray(a) for a in arrays]
         for a in arrays:
             if a.dtype != self.dtype:
@@ -463,14 +524,16 @@ class LatticeKernels:
         shape = self._check_domain(arrays, m, idv)
         self._field_check('force', shape, force, dforce, which, xp_tensor=False)
         self._field_check('omega', shape, omf, domf, which, xp_tensor=False)
-        fn = self._cpu_fn(which)
+        if macro:
+            self._macro_check(which, shape, macro, xp_tensor=False)
+        fn = self._cpu_fn(which, bool(macro))
         # the second pass's scratch (both passes in one call)
         rho = np.empty(self._scratch_shape(shape[:D]), self.dtype) if which == 'adj' and self.link_pass else None
         # ``P`` / ``S``: the table's pointers and strides, each in the table's order
-        ops = self.operands(arrays, m, idv, force, dforce, omf, domf, rho)
-        ptrs = self.pointers(which, ops)
+        ops = self.operands(arrays, m, idv, force, dforce, omf, domf, rho, macro)
+        ptrs = self.pointers(which, ops, bool(macro))
         named = _stride_values(ops, D)
-        strides = [named[a.name] for a in self.table(which) if a.kind == STRIDE]
+        strides = [named[a.name] for a in self.table(which, bool(macro)) if a.kind == STRIDE]
         ext = list(shape[:D]) if D == 3 else [1] + list(shape[:D])
         P = (ctypes.c_void_p * len(ptrs))(*ptrs)
         N = (ctypes.c_longlong * 3)(*ext)
@@ -482,7 +545,8 @@ class LatticeKernels:
 
 class LaunchPlan:
     """One lattice kernel launch with its argument buffer; ``plan(ptrs, stream, omega)`` patches the leading pointer
-    slots (the pdf arrays, then the neighbour mask) and the relaxation rate, and launches on the plan's device
+    slots (the table's pointers: the pdf arrays, the neighbour mask, … and last the density / velocity arrays of an
+    observed step, another slice every launch) and the relaxation rate, and launches on the plan's device
     (made current for the launch when it is not: the function handle belongs to that device's module)."""
     __slots__ = ('fn', 'nblocks', 'template', 'fmt', 'device', 'om_off', 'om_fmt', 'block')
 

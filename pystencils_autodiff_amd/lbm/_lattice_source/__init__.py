@@ -5,7 +5,9 @@ target (HIP / C), the index type, the addressing mode and the adjoint mode — a
 (``lbm_fwd_cell``, ``collision``), the adjoint cell (``lbm_adj_cell``, ``adjoint``: prologue, moment-like sums, force
 adjoint, ω-field adjoint, scatter), the adjoint's second pass (``lbm_adj_rho_cell``, ``links``) and the entry points
 that call them for every cell (``entries``): HIP grid kernels, the HIP fix-up kernel over a cell list, or C loop
-nests. Every kernel's argument list is one table (``args.kernel_args``), which the launcher reads too.
+nests. Every kernel's argument list is one table (``args.kernel_args``), which the launcher reads too. The
+``macroscopic`` variant (``macroscopic``) adds the density / velocity outputs to the forward cell and their adjoint
+seeds to the adjoint cell's load of ``g``; without the flag no line of any source changes.
 
 Adjoint modes. ``programs`` gives per wall id None or the boundary's ``link_program`` (links of the cell's own pdfs the
 fused form does not take, ``boundaries.link_program``; their table rows are zeros): the forward evaluates the link

@@ -1,4 +1,5 @@
 """The adjoint cell in scatter form: prologue, moment-like sums, the force adjoint, the scatter and its stores."""
+from . import macroscopic
 from .addressing import wrap_lines
 from .collision import force_loads, moments, obstacle_copy
 from .common import Fa, axis_sums, c_, cFi, cu_poly, key, mat_row, ncell, signed_sum
@@ -23,8 +24,10 @@ def adjoint_cell(cx, L):
     gcoff = A.cell_offset(L, 'g')
     if s.walls:
         prologue(cx, L, gcoff)
+    macroscopic.cell_offsets(cx, L)
+    macroscopic.adjoint_seeds(cx, L)
     for i in range(cx.Q):
-        L.append(f'  const {ct} g{i} = {A.load("g", i, gcoff)};')
+        L.append(f'  const {ct} g{i} = {A.load("g", i, gcoff)}{macroscopic.seed(cx, i)};')
     force_loads(cx, L)
     omega_load(cx, L)
     cell_density(cx, L)
@@ -185,7 +188,7 @@ def force_adjoint(cx, L):
             # which is ω B_a for SRT (B carries 1/ω) and B_a for TRT / MRT
             sc = '' if s.gsplit else 'omega * '
             val = f'kg * Bf{a} + ({ct})0.5 * {sc}B{a}' + (' * irho' if s.compressible else '')
-        L.append(f'  dforce[(IDX){a} * f_c + fc] += {val};')
+        L.append(f'  dforce[(IDX){a} * f_c + fc] += {val}{macroscopic.force_seed(cx, a)};')
 
 
 def scatter(cx, L, j):

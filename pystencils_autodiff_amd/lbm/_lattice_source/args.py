@@ -10,7 +10,7 @@ KERNELS = ('fwd', 'adj', 'adj_rho', 'adj_fix')
 
 class Arg(NamedTuple):
     """One kernel argument: its name, its kind, the C declaration as printed and the operand group it came with
-    ('pdf': the pdf arrays, the mask and the wall ids; 'force'; 'omega'; 'scratch'; 'fix')."""
+    ('pdf': the pdf arrays, the mask and the wall ids; 'force'; 'omega'; 'scratch'; 'macro'; 'fix')."""
     name: str
     kind: str
     decl: str
@@ -37,6 +37,19 @@ _EXTENTS = [Arg(n, EXTENT, f'const int {n}', 'pdf') for n in 'ZYX']
 _MASK, _IDS = _ptr('nbmask', 'pdf', ty='unsigned'), _ptr('wallid', 'pdf', ty='unsigned char')
 
 
+def macroscopic_pointers(spec, adj):
+    """The 'macro' group's arrays (``macroscopic``), of the compute type, the last pointers of the table: the forward
+    writes ``rho_out`` (strides ``r_*``) and ``vel_out`` (``v_*``); the adjoint reads the seeds ``drho`` / ``dvel``
+    (the same strides) and, for a compressible rule alone, the recorded outputs."""
+    if not spec.mo:
+        return []
+    ty = spec.ctype
+    if not adj:
+        return [_ptr('rho_out', 'macro', const=False, ty=ty), _ptr('vel_out', 'macro', const=False, ty=ty)]
+    out = [_ptr('rho_out', 'macro', ty=ty), _ptr('vel_out', 'macro', ty=ty)] if spec.compressible else []
+    return out + [_ptr('drho', 'macro', ty=ty), _ptr('dvel', 'macro', ty=ty)]
+
+
 def kernel_args(spec, kernel):
     """The arguments of ``lbm_{kernel}`` (``kernel`` in ``KERNELS``) for ``spec``, in the order of the HIP parameter
     list; the C entry points' ``P`` and ``S`` arrays hold the pointer-kind and the stride-kind entries in this order."""
@@ -59,9 +72,11 @@ def kernel_args(spec, kernel):
         A += [_ptr('omf', 'omega')] + ([_ptr('domega', 'omega', const=False)] if adj else [])
     if adj and spec.two:
         A += [_ptr('rho_adj', 'scratch', const=False)]
+    A += macroscopic_pointers(spec, adj)
     A += _EXTENTS + [a for p in pdfs for a in _strides(p, 'qzyx', 'pdf')]
     A += _strides('f', 'czyx', 'force') if spec.ff else []
     A += _strides('w', 'zyx', 'omega') if spec.of else []
+    A += _strides('r', 'zyx', 'macro') + _strides('v', 'czyx', 'macro') if spec.mo else []
     A += [Arg(f'{p}_bytes', REACH, f'const long long {p}_bytes', 'pdf') for p in pdfs]
     # (with an ω field the scalar rate is not what the collision reads: the cell loads ``omega``)
     name = rate_names(spec)[1]

@@ -1,6 +1,7 @@
 """The collision: the cell's force, its moments, the obstacle cells' copy and the forward cell."""
 from .addressing import wrap_lines
 from .common import Fa, c_, cFi, cu_poly, feq, mat_row, shift, signed_sum
+from . import macroscopic
 from .links import cell_density, pull_loads
 from .omega import omega_load
 from .smagorinsky import smagorinsky_moments
@@ -51,14 +52,16 @@ def moments(cx, L):
         L.append(f'  const {ct} ta = ({ct})0.5 * (omega + w_odd), tb = ({ct})0.5 * (omega - w_odd);')
 
 
-def obstacle_copy(cx, L, p, off, sp, soff):
+def obstacle_copy(cx, L, p, off, sp, soff, more=()):
     """An obstacle cell keeps its state (forward: ``dst = src``; adjoint: ``out = g``): array ``sp`` at ``soff`` to
-    array ``p`` at ``off`` (half floats: the bits themselves, no conversion on the way)."""
+    array ``p`` at ``off`` (half floats: the bits themselves, no conversion on the way). ``more``: further lines of
+    the branch."""
     A = cx.A
     L.append(f'  const unsigned msk = nbmask[{cx.cell}];')
     L.append(f'  if ((msk >> {SELF_BIT}) & 1u) {{')
     for i in range(cx.Q):
         L.append('    ' + (A.copy(p, i, off, sp, soff) if cx.s.h else A.store(p, i, off, A.load(sp, i, soff))))
+    L.extend(more)
     L.append('    return;\n  }')
 
 
@@ -77,8 +80,9 @@ def forward_cell(cx, L):
     wrap_lines(L, cx.axes)
     A.neighbour_offsets(L, 's')
     dcoff = A.cell_offset(L, 'd')
+    macroscopic.cell_offsets(cx, L)
     if s.walls:
-        obstacle_copy(cx, L, 'd', dcoff, 's', f'so_{cx.centre}')
+        obstacle_copy(cx, L, 'd', dcoff, 's', f'so_{cx.centre}', macroscopic.obstacle_zero(cx))
 
     force_loads(cx, L)
     omega_load(cx, L)
@@ -93,6 +97,7 @@ def forward_cell(cx, L):
             L.append(f'    fe{i} = {feq(cx, i)}; }}')
         if s.mrt is not None:
             L.append(f'  const {ct} ' + ', '.join(f'nq{k} = f{k} - fe{k}' for k in range(Q)) + ';')   # f − feq
+    macroscopic.forward_sums(cx, L)
     for i in range(Q):
         cu_poly(cx, L, i)
         term = ''
@@ -110,5 +115,7 @@ def forward_cell(cx, L):
             val = f'f{i}' + (f' - omega * ({pw})' if pw else '') + (f' - ({cc})' if cc else '') + term
         else:
             val = f'f{i} + omega * ({feq(cx, i)} - f{i}){term}'
-        L.append('    ' + A.store('d', i, dcoff, val + shift(cx, i, ' - ')) + ' }')
+        val = macroscopic.forward_value(cx, L, i, val + shift(cx, i, ' - '))
+        L.append('    ' + A.store('d', i, dcoff, val) + ' }')
+    macroscopic.forward_store(cx, L)
     L.append('}')

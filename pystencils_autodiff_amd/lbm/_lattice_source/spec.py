@@ -119,6 +119,8 @@ class LatticeSource:
     ω argument or the ω field's value (``smagorinsky.smagorinsky_rate``), and the adjoint carries the chain factors
     ``∂ω_eff/∂f_k`` on the scatter and ``∂ω_eff/∂ω0`` on ``domega`` (``smagorinsky.smagorinsky_adjoint``). Not printed
     for ``half`` pdfs nor with a per-cell force field (whose adjoint would need ∂ω_eff/∂F): ``NotImplementedError``.
+    ``macroscopic``: the forward also writes the density and the velocity of the state it stores, and the adjoint
+    takes their adjoint seeds (``macroscopic.py``); off, every source is what it was without the flag, to the byte.
 
     The derived facts below follow from the fields in ``__post_init__``; a variant (another index type, addressing or
     mode) is made with ``dataclasses.replace``, never by assignment."""
@@ -141,6 +143,7 @@ class LatticeSource:
     zero_centered: bool = False
     half: bool = False
     smagorinsky: object = None
+    macroscopic: bool = False
 
     def __post_init__(self):
         self.hip, self.fix = self.target == 'hip', self.mode == 'fix'
@@ -151,6 +154,7 @@ class LatticeSource:
         self.fm = None if self.force_model is None else str(self.force_model).lower()
         self.ff = bool(self.fm) and bool(self.force_field)
         self.of = bool(self.omega_field)
+        self.mo = bool(self.macroscopic)
         # Guo with TRT / MRT: the force term (prefactor 1 − ω/2 with the shear rate ω, as lbmpy's Guo model) is not
         # relaxed by the collision matrix, so its adjoint sums run over g while the equilibrium's run over h
         self.sm = None if self.smagorinsky is None else float(self.smagorinsky)
