@@ -59,12 +59,14 @@ class SimulationResultsTensors:
         self.output_velocity_tensor = output_velocity_tensor
 
 
-def _lattice_sweeps(step, which, launches, force=None, dforce=None, omf=None, domf=None, macro=None):
+def _lattice_sweeps(step, which, launches, force=None, dforce=None, omf=None, domf=None, macro=None, sof=None,
+                    dsof=None):
     """The lattice kernels over ``launches`` (tensor tuples of ``LatticeKernels.forward`` / ``adjoint``) on the
     current stream: one launch plan per distinct (shapes, strides) — the first, middle and last steps — and only
     the pointers packed per launch. ``force`` (a per-cell force field): bound to every launch; ``dforce``: the
     adjoint launches add their force adjoints into it. ``omf`` / ``domf``: the per-cell relaxation rate and its
-    adjoint, likewise. ``macro``: per launch None, or the density / velocity arrays of an observed step by name
+    adjoint, likewise, and ``sof`` / ``dsof``: the per-cell solid fraction and its adjoint. ``macro``: per launch None,
+    or the density / velocity arrays of an observed step by name
     (``LatticeKernels.operands``) — those launches run the kernels' density / velocity variant, the others the plain
     kernels with no argument more."""
     K = step._lattice_kernels()
@@ -73,32 +75,35 @@ def _lattice_sweeps(step, which, launches, force=None, dforce=None, omf=None, do
     cells = step._cells_arg()
     om = step._omega_of()
     if which != 'adj':
-        dforce = domf = None
+        dforce = domf = dsof = None
     macro = macro or [None] * len(launches)
     if not step._gpu:
         # the C kernels on numpy arrays (both adjoint passes in one call)
         for ts, m in zip(launches, macro):
             if which == 'adj':
-                K.adjoint(*ts, om, mask, ids=ids, force=force, dforce=dforce, omf=omf, domf=domf, **(m or {}))
+                K.adjoint(*ts, om, mask, ids=ids, force=force, dforce=dforce, omf=omf, domf=domf, sof=sof, dsof=dsof,
+                          **(m or {}))
             else:
-                K.forward(*ts, om, mask, ids=ids, force=force, omf=omf, **(m or {}))
+                K.forward(*ts, om, mask, ids=ids, force=force, omf=omf, sof=sof, **(m or {}))
         return
     stream = _torch()._C._cuda_getCurrentRawStream(launches[0][0].device.index)
     rho = K.rho_buffer(launches[0][0]) if which == 'adj' and K.link_pass else None
     # once: the launches differ in their pdf arrays (the leading pointer slots) and, the observed ones, in the
     # density / velocity arrays (the trailing ones)
-    mptr = K.pointers(which, K.operands((), mask, ids, force, dforce, omf, domf, rho))[len(launches[0]):]
+    mptr = K.pointers(which, K.operands((), mask, ids, force, dforce, omf, domf, rho, sof=sof,
+                                        dsof=dsof))[len(launches[0]):]
     mnames = K.table_pointer_names(which, True)[len(launches[0]) + len(mptr):]
     plans = {}
     for ts, m in zip(launches, macro):
         sig = tuple(t.stride() for t in ts) + (m is not None,)
         plan = plans.get(sig)
         if plan is None:
-            plan = plans[sig] = K.plan(which, list(ts), mask, om, ids, force, dforce, omf=omf, domf=domf, macro=m)
+            plan = plans[sig] = K.plan(which, list(ts), mask, om, ids, force, dforce, omf=omf, domf=domf, macro=m,
+                                       sof=sof, dsof=dsof)
         plan(tuple(t.data_ptr() for t in ts) + mptr +
              (tuple(0 if m.get(n) is None else m[n].data_ptr() for n in mnames) if m else ()), stream, om)
         # link-program walls (HIP): the fix-up kernels over the cells next to them
-        K.fix_launch(which, list(ts), mask, om, ids, force, dforce, cells, stream, omf, domf, m)
+        K.fix_launch(which, list(ts), mask, om, ids, force, dforce, cells, stream, omf, domf, m, sof, dsof)
         if rho is not None:
             # the second pass of density-weighted walls (and, on the CPU, link programs) on this launch's output
             K.rho_pass(ts[2], mask, rho, stream)
@@ -135,6 +140,12 @@ def _plain_omega_field(rate, D, dtype):
     return w if np.dtype(w.dtype.numpy_dtype) == np.dtype(dtype) else None
 
 
+def _plain_solid_field(sigma, D, dtype):
+    """The solid-fraction FIELD when the rule's σ is exactly ``s(x)``: a scalar field (no index dimension) of the pdf
+    dtype read at the cell itself, else None."""
+    return _plain_omega_field(sigma, D, dtype)
+
+
 def _guess_src_dst_field_from_update_rule(update_rule, src_hint, dst_hint):
     """``_autodiff_lbstep.py:27-46``: a string hint means "find the one ≥9-component field"."""
     src_candidates = dst_candidates = None
@@ -169,6 +180,8 @@ class AutoDiffLatticeBoltzmannStep:
     ``kernel_params``; a rule whose rate is read from a field (``relaxation_rate=w.center``, a per-cell ω) has no such
     scalar: the field is an additional input of the step, ``create_timestep_op(T).apply(pdfs, *extras)`` in name order,
     and the backward returns its adjoint summed over the steps (a trainable scalar rate: pass ``w0.expand(*domain)``).
+    A rule with a per-cell solid fraction (``solid_fraction=s.center``, partial bounce-back) takes the σ field the same
+    way and returns ``dσ``.
     ``target``: ``'gpu'`` (HIP kernels on torch tensors) or ``'cpu'`` (the C kernels on
     numpy arrays)."""
 
@@ -215,8 +228,10 @@ class AutoDiffLatticeBoltzmannStep:
         if getattr(update_rule, 'stencil', None) is not None and not time_constant_fields and \
                 getattr(update_rule, 'force_model', None) in (None, 'simple') and \
                 not force_is_field(getattr(update_rule, 'force', None)) and not self._additional_fields and \
-                getattr(update_rule, 'smagorinsky', None) is None:
-            # (nor is the Smagorinsky model's rate, a function of the pdfs: the generic derivation as well)
+                getattr(update_rule, 'smagorinsky', None) is None and \
+                getattr(update_rule, 'solid_fraction', None) is None:
+            # (nor is the Smagorinsky model's rate, a function of the pdfs: the generic derivation as well; nor the
+            # partial bounce-back blend of a solid fraction, whatever σ is)
             from ._method import create_lb_adjoint_rule
             backward = create_lb_adjoint_rule(update_rule)
         # the rule's AutoDiffOp (its kernels are the schedule for rules the lattice kernels do not take, and its
@@ -264,8 +279,15 @@ class AutoDiffLatticeBoltzmannStep:
             self._lattice_force = (getattr(update_rule, 'force_model', None),
                                    None if force is None else tuple(float(v) for v in force)) \
                 if force is None or all(sp.sympify(v).is_number for v in force) else None
-        extras_ok = set(self._additional_fields) == {f for f in (self._omega_field, self._force_field)
-                                                     if f is not None}
+        # a per-cell solid fraction read as s(x) (a scalar field of the pdf dtype at the cell itself): the lattice
+        # kernels take the field as an array and accumulate its adjoint; any other σ (a number, a symbol, an offset
+        # read, another dtype) runs on the AutoDiffOp kernels
+        sigma = getattr(update_rule, 'solid_fraction', None)
+        self._solid_field = None if sigma is None else \
+            _plain_solid_field(sigma, src.spatial_dimensions, src.dtype.numpy_dtype)
+        solid_ok = sigma is None or self._solid_field is not None
+        extras_ok = set(self._additional_fields) == {f for f in (self._omega_field, self._force_field,
+                                                                 self._solid_field) if f is not None}
         # TRT: the odd rate from the magic number (a function of the ω argument) or a constant
         self._lattice_trt = None
         trt_ok = True
@@ -308,12 +330,13 @@ class AutoDiffLatticeBoltzmannStep:
         self._lattice = {} if (getattr(update_rule, 'stencil', None) is not None and not time_constant_fields
                                and self._lattice_force is not None and smag_ok
                                and os.environ.get('PSAD_LBM_LATTICE', '1') != '0'
-                               and extras_ok and trt_ok and self._omega_of is not None
+                               and extras_ok and solid_ok and trt_ok and self._omega_of is not None
                                and np.dtype(src.dtype.numpy_dtype) in (np.float16, np.float32, np.float64)
-                               # (float16 pdfs with a force / ω field: the AutoDiffOp kernels — the lattice kernels
-                               # would accumulate the field's adjoint over the steps in float16)
+                               # (float16 pdfs with a force / ω / σ field: the AutoDiffOp kernels — the lattice
+                               # kernels would accumulate the field's adjoint over the steps in float16)
                                and (np.dtype(src.dtype.numpy_dtype) != np.float16 or
-                                    (self._force_field is None and self._omega_field is None))
+                                    (self._force_field is None and self._omega_field is None
+                                     and self._solid_field is None))
                                and (self._force_field is None or
                                     self._force_field.dtype.numpy_dtype == src.dtype.numpy_dtype)) else None
         self._boundary = BoundaryHandling(self.domain_size, on_change=self._flags_changed)
@@ -544,7 +567,7 @@ class AutoDiffLatticeBoltzmannStep:
     def _lattice_kernels(self):
         walls = self._boundary.has_walls
         links, programs = self._link_data()
-        key = (walls, links, programs, self._lattice_smagorinsky)
+        key = (walls, links, programs, self._lattice_smagorinsky, self._solid_field is not None)
         k = self._lattice.get(key)
         if k is None:
             k = self._lattice[key] = LatticeKernels(
@@ -553,7 +576,7 @@ class AutoDiffLatticeBoltzmannStep:
                 trt=self._lattice_trt, programs=programs, mrt=self._lattice_mrt,
                 omega_field=self._omega_field is not None,
                 zero_centered=getattr(self._update_rule, 'zero_centered', False),
-                smagorinsky=self._lattice_smagorinsky)
+                smagorinsky=self._lattice_smagorinsky, solid_field=self._solid_field is not None)
         return k
 
     # -- kernels -----------------------------------------------------------------------------------
@@ -567,7 +590,7 @@ class AutoDiffLatticeBoltzmannStep:
         if self._lattice is not None:
             return self._lattice_kernels().forward(src, dst, self._omega_of(), self._flag_arg(), ids=self._ids_arg(),
                                                    force=self._force_arg(extra), cells=self._cells_arg(),
-                                                   omf=self._omega_arg(extra))
+                                                   omf=self._omega_arg(extra), sof=self._solid_arg(extra))
         kf = self._forward_kernel()
         kf(**{self._pdf_arr_name: src, self._tmp_arr_name: dst}, **extra, **self.kernel_params)
 
@@ -606,8 +629,25 @@ class AutoDiffLatticeBoltzmannStep:
             raise ValueError(f"the update rule reads the relaxation-rate field '{self._omega_field.name}': pass its "
                              "array (extra={name: array})") from None
 
+    def _solid_arg(self, extra):
+        """The per-cell solid-fraction array of the lattice kernels (None without a σ field)."""
+        if self._solid_field is None:
+            return None
+        try:
+            return extra[self._solid_field.name]
+        except (KeyError, TypeError):
+            raise ValueError(f"the update rule reads the solid-fraction field '{self._solid_field.name}': pass its "
+                             "array (extra={name: array})") from None
+
     def _bwd(self, src, diffdst, diffsrc, extra, extra_adj):
         if self._lattice is not None:
+            dsof = None
+            if self._solid_field is not None:
+                name = self._adjoint_name(self._solid_field)
+                if name not in (extra_adj or {}):
+                    raise ValueError(f"the solid-fraction field's adjoint '{name}' needs an array (extra_adj), "
+                                     'accumulated into')
+                dsof = extra_adj[name]
             domf = None
             if self._omega_field is not None:
                 name = self._adjoint_name(self._omega_field)
@@ -623,7 +663,8 @@ class AutoDiffLatticeBoltzmannStep:
                 dforce = extra_adj[name]
             return self._lattice_kernels().adjoint(src, diffdst, diffsrc, self._omega_of(), self._flag_arg(),
                                                    ids=self._ids_arg(), force=self._force_arg(extra), dforce=dforce,
-                                                   cells=self._cells_arg(), omf=self._omega_arg(extra), domf=domf)
+                                                   cells=self._cells_arg(), omf=self._omega_arg(extra), domf=domf,
+                                                   sof=self._solid_arg(extra), dsof=dsof)
         _, kb = self._kernels()
         kb(**{self._pdf_arr_name: src, 'diff' + self._tmp_arr_name: diffdst, 'diff' + self._pdf_arr_name: diffsrc},
            **extra, **extra_adj, **self.kernel_params)
@@ -727,7 +768,7 @@ class AutoDiffLatticeBoltzmannStep:
                 if lattice:
                     states = [x0] + step._internal_states(T - 1) + [step._alloc(zero=False)]
                     _lattice_sweeps(step, 'fwd', [(states[t], states[t + 1]) for t in range(T)],
-                                    step._force_arg(ex), omf=step._omega_arg(ex))
+                                    step._force_arg(ex), omf=step._omega_arg(ex), sof=step._solid_arg(ex))
                 else:
                     states = [x0]
                     for t in range(T):
@@ -778,11 +819,13 @@ class AutoDiffLatticeBoltzmannStep:
                     if not extras:
                         _lattice_sweeps(step, 'adj', launches)
                         return out
-                    # the force / ω adjoint: every step's adjoint launch adds its share into one array, zeroed once
-                    F, W = step._force_arg(ex), step._omega_arg(ex)
+                    # the force / ω / σ adjoint: every step's adjoint launch adds its share into one array, zeroed
+                    # once
+                    F, W, S = step._force_arg(ex), step._omega_arg(ex), step._solid_arg(ex)
                     dex = {f.name: torch.zeros_like(ex[f.name]) for f in extras}
                     _lattice_sweeps(step, 'adj', launches, F, None if F is None else dex[step._force_field.name],
-                                    W, None if W is None else dex[step._omega_field.name])
+                                    W, None if W is None else dex[step._omega_field.name],
+                                    sof=S, dsof=None if S is None else dex[step._solid_field.name])
                     return (out, *[dex[f.name] for f in extras])
                 cur = g
                 acc = {n: torch.zeros_like(x) for n, x in ex.items()}
@@ -866,7 +909,7 @@ class AutoDiffLatticeBoltzmannStep:
                 for t, j in slot.items():
                     macro[t] = dict(rho_out=arrays(rho[j]), vel_out=arrays(vel[j]))
                 _lattice_sweeps(step, 'fwd', [(states[t], states[t + 1]) for t in range(T)], step._force_arg(ex),
-                                omf=step._omega_arg(ex), macro=macro)
+                                omf=step._omega_arg(ex), macro=macro, sof=step._solid_arg(ex))
                 ctx.input_is_state0 = gpu and states[0].data_ptr() == pdfs.data_ptr()
                 ctx.records = states[1:-1] if ctx.input_is_state0 else states[:-1]
                 out = states[-1] if gpu else torch.from_numpy(states[-1])
@@ -907,11 +950,12 @@ class AutoDiffLatticeBoltzmannStep:
                     macro.append(None if j is None else dict(rho_out=arrays(rho[j]), vel_out=arrays(vel[j]),
                                                              drho=arrays(drho[j]), dvel=arrays(dvel[j])))
                     cur = nxt
-                # the force / ω adjoint: every step's adjoint launch adds its share into one array, zeroed once
-                F, W = step._force_arg(ex), step._omega_arg(ex)
+                # the force / ω / σ adjoint: every step's adjoint launch adds its share into one array, zeroed once
+                F, W, S = step._force_arg(ex), step._omega_arg(ex), step._solid_arg(ex)
                 dex = {f.name: (torch.zeros_like if gpu else np.zeros_like)(ex[f.name]) for f in extras}
                 _lattice_sweeps(step, 'adj', launches, F, None if F is None else dex[step._force_field.name],
-                                W, None if W is None else dex[step._omega_field.name], macro=macro)
+                                W, None if W is None else dex[step._omega_field.name], macro=macro,
+                                sof=S, dsof=None if S is None else dex[step._solid_field.name])
                 if not gpu:
                     return (torch.from_numpy(out), *[torch.from_numpy(dex[f.name]) for f in extras])
                 return (out, *[dex[f.name] for f in extras])

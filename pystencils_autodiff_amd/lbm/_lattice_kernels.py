@@ -105,7 +105,8 @@ def lattice_strides(t, D):
 
 def _stride_values(ops, D):
     """name → value of every stride argument the operands ``ops`` give: ``{p}_{q,z,y,x}`` of the pdf arrays,
-    ``f_{c,z,y,x}`` of the force field, ``w_{z,y,x}`` of the ω field (2-D: the z strides are 0)."""
+    ``f_{c,z,y,x}`` of the force field, ``w_{z,y,x}`` of the ω field, ``p_{z,y,x}`` of the σ field (2-D: the z strides
+    are 0)."""
     v = {}
     for p, t in [(p, ops.get(name)) for p, name in ARRAYS.items()] + [('f', ops.get('force'))]:
         if t is not None:
@@ -113,6 +114,9 @@ def _stride_values(ops, D):
     if ops.get('omf') is not None:
         sw = _element_strides(ops['omf'])
         v.update(zip(('w_z', 'w_y', 'w_x'), [0] * (3 - len(sw)) + sw))
+    if ops.get('sigf') is not None:
+        sp_ = _element_strides(ops['sigf'])
+        v.update(zip(('p_z', 'p_y', 'p_x'), [0] * (3 - len(sp_)) + sp_))
     # the density / velocity outputs and their seeds (one set of strides: the seeds have the outputs' layout)
     rho = ops.get('rho_out') if ops.get('rho_out') is not None else ops.get('drho')
     vel = ops.get('vel_out') if ops.get('vel_out') is not None else ops.get('dvel')
@@ -140,7 +144,7 @@ class LatticeKernels:
 
     def __init__(self, stencil, compressible, dtype, walls, target, links=None, force_model=None, force=None,
                  force_field=False, trt=None, programs=None, mrt=None, *, omega_field=False, zero_centered=False,
-                 smagorinsky=None):
+                 smagorinsky=None, solid_field=False):
         self.stencil = stencil
         # the Smagorinsky constant C_s (None: no subgrid model): a constant of the emitted source, so of every cache
         # key made from it
@@ -149,6 +153,9 @@ class LatticeKernels:
         self.zero_centered = bool(zero_centered)
         # ω read per cell from a scalar field ``[*domain]``, its adjoint accumulated by the adjoint launches
         self.omega_field = bool(omega_field)
+        # the solid fraction σ read per cell from a scalar field ``[*domain]`` (partial bounce-back), its adjoint
+        # accumulated by the adjoint launches
+        self.solid_field = bool(solid_field)
         # MRT: (P_ω, C) relaxation matrices as float tuples (``_method.mrt_relaxation_matrices``)
         self.mrt = None if mrt is None else tuple(tuple(tuple(float(v) for v in row) for row in M) for M in mrt)
         self.trt = None if trt is None else (str(trt[0]), float(trt[1]))
@@ -169,7 +176,7 @@ class LatticeKernels:
             stencil, self.compressible, self.ct, self.walls, self.links, programs, force_model, self.force,
             self.force_field, self.trt, self.mrt, target='hip' if target == 'gpu' else 'c',
             omega_field=self.omega_field, zero_centered=self.zero_centered, half=self.dtype == np.float16,
-            smagorinsky=self.smagorinsky)
+            smagorinsky=self.smagorinsky, solid_field=self.solid_field)
         # density-weighted links: the adjoint takes a second pass (lbm_adj_rho) over a per-cell scratch array
         self.rho_links = spec.rho_links
         # link programs (boundaries.link_program). C: inline, a Q-component scratch array per cell and the second
@@ -261,12 +268,15 @@ class LatticeKernels:
             raise ValueError('the periodic lattice needs at least 2 cells per axis')
 
     @staticmethod
-    def operands(tensors, mask, ids, force=None, dforce=None, omf=None, domf=None, scratch=None, macro=None):
+    def operands(tensors, mask, ids, force=None, dforce=None, omf=None, domf=None, scratch=None, macro=None,
+                 sof=None, dsof=None):
         """Argument name → operand (torch tensors, or numpy arrays on the C path; None: not given) of ``lbm_fwd``
         (``tensors``: src, dst) or ``lbm_adj`` / ``lbm_adj_fix`` (src, g, out). ``macro``: None, or by name the arrays
-        of the density / velocity variant (``rho_out``, ``vel_out``, ``drho``, ``dvel``)."""
+        of the density / velocity variant (``rho_out``, ``vel_out``, ``drho``, ``dvel``). ``sof`` / ``dsof``: the solid
+        fraction and its adjoint."""
         return dict(zip(('src', 'dst') if len(tensors) == 2 else ('src', 'g', 'out'), tensors), nbmask=mask,
-                    wallid=ids, force=force, dforce=dforce, omf=omf, domega=domf, rho_adj=scratch, **(macro or {}))
+                    wallid=ids, force=force, dforce=dforce, omf=omf, domega=domf, sigf=sof, dsolid=dsof, rho_adj=scratch,
+                    **(macro or {}))
 
     def pointers(self, kernel, ops, macro=False):
         """The pointer slots a launch of ``lbm_{kernel}`` patches, in the table's order, from the operands ``ops``
@@ -329,23 +339,26 @@ class LatticeKernels:
             addr = 'ptr'
         return idx, addr
 
-    def _launch_mode(self, tensors, force=None, dforce=None, omf=None, domf=None, *more):
-        """``(idx, addr)`` of a ``plan()`` launch: ``_mode`` of the pdf tensors; the force and the ω field (and
+    def _launch_mode(self, tensors, force=None, dforce=None, omf=None, domf=None, *more, sof=None, dsof=None):
+        """``(idx, addr)`` of a ``plan()`` launch: ``_mode`` of the pdf tensors; the force, the ω and the σ field (and
         their adjoints) are read through plain pointers with IDX offsets, so a far-reaching one widens ``idx`` alone."""
         idx, addr = self._mode(tensors)
-        if max([self._reach(t) for t in (force, dforce, omf, domf) + more if t is not None], default=0) >= 2 ** 31 - 1:
+        if max([self._reach(t) for t in (force, dforce, omf, domf, sof, dsof) + more if t is not None],
+               default=0) >= 2 ** 31 - 1:
             idx = 'long long'
         return idx, addr
 
     def _field_check(self, kind, shape, field, adjoint, which, xp_tensor=True):
-        """A per-cell field ``kind`` — 'force': ``[*domain, D]``, 'omega' (the relaxation rate): ``[*domain]`` — and, for
-        the adjoint kernel, its accumulated adjoint: both of the pdf dtype, ``adjoint`` with the strides of ``field``;
+        """A per-cell field ``kind`` — 'force': ``[*domain, D]``, 'omega' (the relaxation rate) / 'solid' (the solid
+        fraction): ``[*domain]`` — and, for the adjoint kernel, its accumulated adjoint: both of the pdf dtype,
+        ``adjoint`` with the strides of ``field``;
         none where the kernels take no such field."""
         D = self.stencil.D
         on, want = (self.force_field, tuple(shape[:D]) + (D,)) if kind == 'force' else \
-            (self.omega_field, tuple(shape[:D]))
+            (self.omega_field if kind == 'omega' else self.solid_field, tuple(shape[:D]))
         what, kernels, name, short = ('force field', 'force-field', 'force', 'force') if kind == 'force' else \
-            ('relaxation-rate field', 'ω-field', 'relaxation-rate field', 'relaxation-rate')
+            ('relaxation-rate field', 'ω-field', 'relaxation-rate field', 'relaxation-rate') if kind == 'omega' else \
+            ('solid-fraction field', 'σ-field', 'solid-fraction field', 'solid-fraction')
         need = [field] + ([adjoint] if which == 'adj' else [])
         if not on:
             if field is not None or adjoint is not None:
@@ -364,17 +377,18 @@ class LatticeKernels:
             raise ValueError(f'the {short} adjoint must have the strides of the {name}')
 
     def plan(self, which, tensors, mask, omega, ids=None, force=None, dforce=None, fix=None, omf=None, domf=None,
-             macro=None):
+             macro=None, sof=None, dsof=None):
         """The launch of ``which`` ('fwd' / 'adj') on tensors of these shapes, strides, dtype and device (with or
         without walls): a ``LaunchPlan`` whose pointer slots and relaxation rate are patched per launch — the
         time-step op launches T of them per apply. ω is not part of the key (a trained or scheduled rate reuses the
         plan); the plan is built with the first ω it sees. ``fix``: (cells,) — the fix-up kernel of ``which`` over
         the listed cells (int32 cell indices). ``macro``: the arrays of the density / velocity variant (``operands``),
-        whose pointers every launch patches too."""
+        whose pointers every launch patches too. ``sof`` / ``dsof``: the per-cell solid fraction and its adjoint."""
         key = (which, mask is not None) + tuple((tuple(t.shape), tuple(t.stride()), t.dtype, t.device)
                                                 for t in tensors) + \
             ((tuple(force.shape), tuple(force.stride())) if force is not None else ()) + \
             (('omf', tuple(omf.shape), tuple(omf.stride())) if omf is not None else ()) + \
+            (('sof', tuple(sof.shape), tuple(sof.stride())) if sof is not None else ()) + \
             ((fix[0].data_ptr(), int(fix[0].numel())) if fix is not None else ()) + \
             (('macro',) + tuple((n, tuple(t.stride())) for n, t in sorted(macro.items()) if t is not None)
              if macro else ())
@@ -386,10 +400,13 @@ class LatticeKernels:
             raise ValueError('the density / velocity arrays must be on the pdf tensors\' device')
         self._field_check('force', tuple(tensors[0].shape), force, dforce, which)
         self._field_check('omega', tuple(tensors[0].shape), omf, domf, which)
+        self._field_check('solid', tuple(tensors[0].shape), sof, dsof, which)
         self._check(tensors, mask, ids)
         if any(t is not None and (not t.is_cuda or t.device != tensors[0].device) for t in (omf, domf)):
             raise ValueError('the relaxation-rate field must be on the pdf tensors\' device')
-        idx, addr = self._launch_mode(tensors, force, dforce, omf, domf, *marr)
+        if any(t is not None and (not t.is_cuda or t.device != tensors[0].device) for t in (sof, dsof)):
+            raise ValueError('the solid-fraction field must be on the pdf tensors\' device')
+        idx, addr = self._launch_mode(tensors, force, dforce, omf, domf, *marr, sof=sof, dsof=dsof)
         dev = tensors[0].device.index
         # (the fix-up kernel: the cell list and its length after the main kernel's arguments)
         kernel = which + ('_fix' if fix is not None else '')
@@ -398,7 +415,7 @@ class LatticeKernels:
         nblocks = self._blocks(X, Y, Z) if fix is None else -(-int(fix[0].numel()) // FIX_BLOCK)
         table = self.table(kernel, bool(macro))
         fmt = struct_format(table, idx, self.ct)
-        ops = dict(self.operands(tensors, mask, ids, force, dforce, omf, domf, macro=macro),
+        ops = dict(self.operands(tensors, mask, ids, force, dforce, omf, domf, macro=macro, sof=sof, dsof=dsof),
                    cells=fix[0] if fix else None)
         om_i = [a.kind for a in table].index(RATE)
         nptr = len((self._mptr_names if macro else self._ptr_names)[which])
@@ -409,7 +426,7 @@ class LatticeKernels:
         return plan
 
     def fix_launch(self, which, tensors, mask, omega, ids, force, dforce, cells, stream, omf=None, domf=None,
-                   macro=None):
+                   macro=None, sof=None, dsof=None):
         """The fix-up launch after a main adjoint launch on ``tensors`` (HIP with link programs; nothing for the
         forward, which runs them inline, or when no cell is listed): the listed cells' adjoint with their programs'
         Jacobian terms, added atomically into the entries the main launch left zeroed (no second fix-up launch)."""
@@ -417,9 +434,9 @@ class LatticeKernels:
                 int(cells.numel()) == 0:
             return
         plan = self.plan(which, tensors, mask, omega, ids, force, dforce, fix=(cells,), omf=omf, domf=domf,
-                         macro=macro)
+                         macro=macro, sof=sof, dsof=dsof)
         rho = self.rho_buffer(tensors[0]) if self.link_pass else None
-        plan(self.pointers(which, self.operands(tensors, mask, ids, force, dforce, omf, domf, rho, macro),
+        plan(self.pointers(which, self.operands(tensors, mask, ids, force, dforce, omf, domf, rho, macro, sof, dsof),
                            bool(macro)), stream, omega)
 
     def _scratch_shape(self, domain):
@@ -457,35 +474,38 @@ class LatticeKernels:
         return plan
 
     def forward(self, src, dst, omega, mask=None, stream=None, ids=None, force=None, cells=None, omf=None,
-                rho_out=None, vel_out=None):
+                rho_out=None, vel_out=None, sof=None):
         """``dst = stream-pull-collide(src)`` (torch tensors ``[*domain, q]``, any strides; ``force``: the per-cell
         force ``[*domain, D]`` of force-field kernels; ``omf``: the per-cell relaxation rate ``[*domain]`` of ω-field
-        kernels, which ignore ``omega``). ``rho_out`` / ``vel_out`` (both or neither; the compute type, ``[*domain]``
+        kernels, which ignore ``omega``; ``sof``: the per-cell solid fraction ``[*domain]`` of σ-field kernels).
+        ``rho_out`` / ``vel_out`` (both or neither; the compute type, ``[*domain]``
         and ``[*domain, D]``, any strides): also written, the density and the velocity of ``dst`` — 0 in obstacle
         cells — by the kernels' density / velocity variant."""
         macro = None if rho_out is None and vel_out is None else dict(rho_out=rho_out, vel_out=vel_out)
         if self.target != 'gpu':
-            return self._cpu('fwd', [src, dst], omega, mask, ids, force, omf=omf, macro=macro)
+            return self._cpu('fwd', [src, dst], omega, mask, ids, force, omf=omf, macro=macro, sof=sof)
         st = _stream(stream, src)
-        self.plan('fwd', [src, dst], mask, omega, ids, force, omf=omf, macro=macro)(
-            self.pointers('fwd', self.operands([src, dst], mask, ids, force, omf=omf, macro=macro), bool(macro)),
-            st, omega)
+        self.plan('fwd', [src, dst], mask, omega, ids, force, omf=omf, macro=macro, sof=sof)(
+            self.pointers('fwd', self.operands([src, dst], mask, ids, force, omf=omf, macro=macro, sof=sof),
+                          bool(macro)), st, omega)
 
     def adjoint(self, src, g, out, omega, mask=None, stream=None, ids=None, force=None, dforce=None, cells=None,
-                omf=None, domf=None, rho_out=None, vel_out=None, drho=None, dvel=None):
+                omf=None, domf=None, rho_out=None, vel_out=None, drho=None, dvel=None, sof=None, dsof=None):
         """``out = (∂ step / ∂ src)ᵀ g`` at the state ``src``; force-field kernels also ADD ``(∂ step / ∂ F)ᵀ g`` to
-        ``dforce``, ω-field kernels ``(∂ step / ∂ ω)ᵀ g`` to ``domf``. ``drho`` / ``dvel`` (both or neither): the
+        ``dforce``, ω-field kernels ``(∂ step / ∂ ω)ᵀ g`` to ``domf``, σ-field kernels ``(∂ step / ∂ σ)ᵀ g`` to ``dsof``.
+        ``drho`` / ``dvel`` (both or neither): the
         adjoint seeds of the density and the velocity of this step's output, added to ``g`` in the cell (with the
         recorded ``rho_out`` / ``vel_out`` of that step, which a compressible rule reads)."""
         macro = None if drho is None and dvel is None else dict(rho_out=rho_out, vel_out=vel_out, drho=drho, dvel=dvel)
         if self.target != 'gpu':
-            return self._cpu('adj', [src, g, out], omega, mask, ids, force, dforce, omf, domf, macro)
+            return self._cpu('adj', [src, g, out], omega, mask, ids, force, dforce, omf, domf, macro, sof, dsof)
         st = _stream(stream, src)
         rho = self.rho_buffer(src) if self.link_pass else None
-        self.plan('adj', [src, g, out], mask, omega, ids, force, dforce, omf=omf, domf=domf, macro=macro)(
-            self.pointers('adj', self.operands([src, g, out], mask, ids, force, dforce, omf, domf, rho, macro),
-                          bool(macro)), st, omega)
-        self.fix_launch('adj', [src, g, out], mask, omega, ids, force, dforce, cells, st, omf, domf, macro)
+        self.plan('adj', [src, g, out], mask, omega, ids, force, dforce, omf=omf, domf=domf, macro=macro, sof=sof,
+                  dsof=dsof)(
+            self.pointers('adj', self.operands([src, g, out], mask, ids, force, dforce, omf, domf, rho, macro, sof,
+                                               dsof), bool(macro)), st, omega)
+        self.fix_launch('adj', [src, g, out], mask, omega, ids, force, dforce, cells, st, omf, domf, macro, sof, dsof)
         if rho is not None:
             self.rho_pass(out, mask, rho, st)
 
@@ -513,7 +533,8 @@ class LatticeKernels:
             fn = self._fns[key] = compile_c(self.source(macro=macro), f'lbm_{which}', openmp=True)
         return fn
 
-    def _cpu(self, which, arrays, omega, mask, ids=None, force=None, dforce=None, omf=None, domf=None, macro=None):
+    def _cpu(self, which, arrays, omega, mask, ids=None, force=None, dforce=None, omf=None, domf=None, macro=None,
+             sof=None, dsof=None):
         arrays = [np.asarray(a) for a in arrays]
         for a in arrays:
             if a.dtype != self.dtype:
@@ -524,13 +545,14 @@ class LatticeKernels:
         shape = self._check_domain(arrays, m, idv)
         self._field_check('force', shape, force, dforce, which, xp_tensor=False)
         self._field_check('omega', shape, omf, domf, which, xp_tensor=False)
+        self._field_check('solid', shape, sof, dsof, which, xp_tensor=False)
         if macro:
             self._macro_check(which, shape, macro, xp_tensor=False)
         fn = self._cpu_fn(which, bool(macro))
         # the second pass's scratch (both passes in one call)
         rho = np.empty(self._scratch_shape(shape[:D]), self.dtype) if which == 'adj' and self.link_pass else None
         # ``P`` / ``S``: the table's pointers and strides, each in the table's order
-        ops = self.operands(arrays, m, idv, force, dforce, omf, domf, rho, macro)
+        ops = self.operands(arrays, m, idv, force, dforce, omf, domf, rho, macro, sof, dsof)
         ptrs = self.pointers(which, ops, bool(macro))
         named = _stride_values(ops, D)
         strides = [named[a.name] for a in self.table(which, bool(macro)) if a.kind == STRIDE]

@@ -8,6 +8,9 @@ that call them for every cell (``entries``): HIP grid kernels, the HIP fix-up ke
 nests. Every kernel's argument list is one table (``args.kernel_args``), which the launcher reads too. The
 ``macroscopic`` variant (``macroscopic``) adds the density / velocity outputs to the forward cell and their adjoint
 seeds to the adjoint cell's load of ``g``; without the flag no line of any source changes.
+The ``solid_field`` variant (``solid``) blends the forward cell's stored value with the arriving population of the opposite
+direction by a per-cell solid fraction σ, blends the adjoint cell's ``v_j`` likewise and accumulates ``dσ``; without the
+flag no line of any source changes either.
 
 Adjoint modes. ``programs`` gives per wall id None or the boundary's ``link_program`` (links of the cell's own pdfs the
 fused form does not take, ``boundaries.link_program``; their table rows are zeros): the forward evaluates the link

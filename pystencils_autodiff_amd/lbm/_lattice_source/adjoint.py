@@ -2,11 +2,12 @@
 from . import macroscopic
 from .addressing import wrap_lines
 from .collision import force_loads, moments, obstacle_copy
-from .common import Fa, axis_sums, c_, cFi, cu_poly, key, mat_row, ncell, signed_sum
+from .common import Fa, axis_sums, c_, cFi, cu_poly, key, ncell, signed_sum
 from .links import (cell_density, fix_loads, program_cases, pull_loads, rho_slot, scatter_programs_fix,
                     scatter_programs_inline)
 from .omega import omega_adjoint, omega_adjoint_pdfs, omega_load
 from .smagorinsky import sm_fold, sm_P, smagorinsky_adjoint
+from .solid import adjoint_blend, field_scale, mrt_h, solid_adjoint, solid_adjoint_pdfs, solid_load
 from .spec import FIX_BIT
 
 
@@ -30,6 +31,7 @@ def adjoint_cell(cx, L):
         L.append(f'  const {ct} g{i} = {A.load("g", i, gcoff)}{macroscopic.seed(cx, i)};')
     force_loads(cx, L)
     omega_load(cx, L)
+    solid_load(cx, L)
     cell_density(cx, L)
     listed = s.fix and bool(s.gq_all)
     if listed:
@@ -37,6 +39,7 @@ def adjoint_cell(cx, L):
     pull_loads(cx, L, cx.adj_progs, hoisted=listed and s.walls)
     moments(cx, L)
     omega_adjoint_pdfs(cx, L)
+    solid_adjoint_pdfs(cx, L)
     smagorinsky_adjoint(cx, L)
     if s.rho_links:
         L.append(f'  {ct} Rr = 0;')             # Σ_j βρ_j v_j over the cell's density-weighted links
@@ -46,6 +49,7 @@ def adjoint_cell(cx, L):
     adjoint_sums(cx, L)
     force_adjoint(cx, L)
     omega_adjoint(cx, L)
+    solid_adjoint(cx, L)
     if s.compressible:
         L.append(f'  const {ct} Bu = ' + ' + '.join(f'B{a} * u{a}' for a in range(cx.D)) + ';')
     for j in range(cx.Q):
@@ -102,12 +106,9 @@ def adjoint_sums(cx, L):
     TRT takes them over h_i = a g_i + b g_ī: ``v_j = (1 − a) g_j − b g_ĵ + A_h + Σ_a B_h,a ∂u_a/∂f_j``; MRT over
     h = Aᵀ g: ``v_j = g_j − h_j + A_h + Σ_a B_h,a ∂u_a/∂f_j``."""
     s, ct, D, w = cx.s, cx.ct, cx.D, cx.w
-    if s.mrt is not None:
-        # h = Aᵀ g
-        for i in range(cx.Q):
-            pw, cc = mat_row(cx, s.mrt[0], 'g', i, True), mat_row(cx, s.mrt[1], 'g', i, True)
-            hv = ' + '.join(t for t in ((f'omega * ({pw})' if pw else None), (f'({cc})' if cc else None)) if t)
-            L.append(f'  const {ct} h{i} = {hv or c_(cx, 0)};')
+    if s.mrt is not None and not s.sf:
+        # h = Aᵀ g (with a solid fraction ``solid_adjoint_pdfs`` has formed it already)
+        mrt_h(cx, L)
     L.append(f'  {ct} S = 0, A = 0;')
     if s.gsplit:
         L.append(f'  {ct} Sg = 0;')                   # Σ_i g_i w_i (the force term's sums run over g)
@@ -188,7 +189,7 @@ def force_adjoint(cx, L):
             # which is ω B_a for SRT (B carries 1/ω) and B_a for TRT / MRT
             sc = '' if s.gsplit else 'omega * '
             val = f'kg * Bf{a} + ({ct})0.5 * {sc}B{a}' + (' * irho' if s.compressible else '')
-        L.append(f'  dforce[(IDX){a} * f_c + fc] += {val}{macroscopic.force_seed(cx, a)};')
+        L.append(f'  dforce[(IDX){a} * f_c + fc] += {field_scale(cx, val)}{macroscopic.force_seed(cx, a)};')
 
 
 def scatter(cx, L, j):
@@ -205,15 +206,16 @@ def scatter(cx, L, j):
     sm = '' if s.sm is None else (f' + sm_l * {sm_P(cx, j)}' if sm_P(cx, j) else '') + \
         (' - sm_c' if s.compressible else '')
     if s.trt is not None and inv[j] != j:
-        L.append(f'  {{ {vq}{ct} v = (({ct})1 - ta) * g{j} - tb * g{inv[j]} + (A + {du}){sm};')
+        v = f'(({ct})1 - ta) * g{j} - tb * g{inv[j]} + (A + {du}){sm}'
     elif s.trt is not None:
-        L.append(f'  {{ {vq}{ct} v = (({ct})1 - omega) * g{j} + (A + {du}){sm};')
+        v = f'(({ct})1 - omega) * g{j} + (A + {du}){sm}'
     elif s.mrt is not None:
-        L.append(f'  {{ {vq}{ct} v = g{j} - h{j} + (A + {du}){sm};')
+        v = f'g{j} - h{j} + (A + {du}){sm}'
     elif s.sm is not None:
-        L.append(f'  {{ {vq}{ct} v = (({ct})1 - omega) * g{j} + (A + {du}){sm};')
+        v = f'(({ct})1 - omega) * g{j} + (A + {du}){sm}'
     else:
-        L.append(f'  {{ {vq}{ct} v = (({ct})1 - omega) * g{j} + omega * (A + {du});')
+        v = f'(({ct})1 - omega) * g{j} + omega * (A + {du})'
+    L.append(f'  {{ {vq}{ct} v = {adjoint_blend(cx, j, v)};')
     taken = ''                  # (fix-up kernel) guard of the scatter store: not where a neighbour link is taken
     if linked:
         if s.rho_links:

@@ -10,7 +10,7 @@ KERNELS = ('fwd', 'adj', 'adj_rho', 'adj_fix')
 
 class Arg(NamedTuple):
     """One kernel argument: its name, its kind, the C declaration as printed and the operand group it came with
-    ('pdf': the pdf arrays, the mask and the wall ids; 'force'; 'omega'; 'scratch'; 'macro'; 'fix')."""
+    ('pdf': the pdf arrays, the mask and the wall ids; 'force'; 'omega'; 'solid'; 'scratch'; 'macro'; 'fix')."""
     name: str
     kind: str
     decl: str
@@ -70,12 +70,15 @@ def kernel_args(spec, kernel):
         A += [_ptr('force', 'force')] + ([_ptr('dforce', 'force', const=False)] if adj else [])
     if spec.of:
         A += [_ptr('omf', 'omega')] + ([_ptr('domega', 'omega', const=False)] if adj else [])
+    if spec.sf:
+        A += [_ptr('sigf', 'solid')] + ([_ptr('dsolid', 'solid', const=False)] if adj else [])
     if adj and spec.two:
         A += [_ptr('rho_adj', 'scratch', const=False)]
     A += macroscopic_pointers(spec, adj)
     A += _EXTENTS + [a for p in pdfs for a in _strides(p, 'qzyx', 'pdf')]
     A += _strides('f', 'czyx', 'force') if spec.ff else []
     A += _strides('w', 'zyx', 'omega') if spec.of else []
+    A += _strides('p', 'zyx', 'solid') if spec.sf else []
     A += _strides('r', 'zyx', 'macro') + _strides('v', 'czyx', 'macro') if spec.mo else []
     A += [Arg(f'{p}_bytes', REACH, f'const long long {p}_bytes', 'pdf') for p in pdfs]
     # (with an ω field the scalar rate is not what the collision reads: the cell loads ``omega``)

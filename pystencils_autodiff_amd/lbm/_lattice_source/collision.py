@@ -5,6 +5,7 @@ from . import macroscopic
 from .links import cell_density, pull_loads
 from .omega import omega_load
 from .smagorinsky import smagorinsky_moments
+from .solid import forward_blend, solid_load
 from .spec import SELF_BIT
 
 
@@ -86,6 +87,7 @@ def forward_cell(cx, L):
 
     force_loads(cx, L)
     omega_load(cx, L)
+    solid_load(cx, L)
     cell_density(cx, L)
     pull_loads(cx, L)
     moments(cx, L)
@@ -115,7 +117,7 @@ def forward_cell(cx, L):
             val = f'f{i}' + (f' - omega * ({pw})' if pw else '') + (f' - ({cc})' if cc else '') + term
         else:
             val = f'f{i} + omega * ({feq(cx, i)} - f{i}){term}'
-        val = macroscopic.forward_value(cx, L, i, val + shift(cx, i, ' - '))
+        val = macroscopic.forward_value(cx, L, i, forward_blend(cx, i, val) + shift(cx, i, ' - '))
         L.append('    ' + A.store('d', i, dcoff, val) + ' }')
     macroscopic.forward_store(cx, L)
     L.append('}')

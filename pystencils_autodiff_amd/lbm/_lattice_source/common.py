@@ -42,6 +42,8 @@ class Context:
         self.fstr_unused = '(void)f_z; ' if s.ff and self.D == 2 else ''
         if s.of:
             self.fstr_unused += '(void)omega_s; ' + ('(void)w_z; ' if self.D == 2 else '')
+        if s.sf and self.D == 2:
+            self.fstr_unused += '(void)p_z; '
 
 
 def c_(cx, v):

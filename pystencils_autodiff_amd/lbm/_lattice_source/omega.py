@@ -1,5 +1,6 @@
 """The per-cell relaxation rate (``omega_field``): its load and the adjoint ``dω`` (Smagorinsky's chain starts from it)."""
 from .common import c_, cFi, cu_poly, feq, mat_row
+from .solid import field_scale
 
 
 def omega_load(cx, L):
@@ -57,7 +58,7 @@ def omega_adjoint(cx, L):
     if not s.of or s.sm is not None:
         return                                  # (Smagorinsky: ``smagorinsky_adjoint`` has stored it already)
     omega_adjoint_equilibria(cx, L)
-    L.append('  domega[wc] += (T)dom;')
+    L.append('  domega[wc] += (T)' + (f'({field_scale(cx, "dom")})' if s.sf else 'dom') + ';')
 
 
 def omega_adjoint_equilibria(cx, L):

@@ -76,7 +76,7 @@ def smagorinsky_adjoint(cx, L):
     if s.compressible:
         L.append(f'  const {ct} sm_c = sm_k * sm_q * irho;')
     if s.of:
-        L.append(f'  domega[wc] += (T)(dom * omega * omega * (({ct})1 + (({ct})1 / {cx.om0}) / sm_R) / '
+        L.append(f'  domega[wc] += (T)({"sfr1 * " if s.sf else ""}dom * omega * omega * (({ct})1 + (({ct})1 / {cx.om0}) / sm_R) / '
                  f'(({ct})2 * {cx.om0} * {cx.om0}));')
 
 

@@ -121,6 +121,10 @@ class LatticeSource:
     for ``half`` pdfs nor with a per-cell force field (whose adjoint would need ∂ω_eff/∂F): ``NotImplementedError``.
     ``macroscopic``: the forward also writes the density and the velocity of the state it stores, and the adjoint
     takes their adjoint seeds (``macroscopic.py``); off, every source is what it was without the flag, to the byte.
+    ``solid_field``: a per-cell solid fraction σ ``[*domain]`` read by strides (partial bounce-back): the forward stores
+    ``(1 − σ) c_i + σ f_ī``, the adjoint blends ``v_j`` likewise, scales ``dω`` / ``dF`` by ``1 − σ`` and ACCUMULATES
+    ``dσ(x) = Σ_i g_i (f_ī − c_i)`` into ``dsolid`` (``solid.py``); off, no line of any source changes. Not printed
+    for ``half`` pdfs (``NotImplementedError``, as the ω field).
 
     The derived facts below follow from the fields in ``__post_init__``; a variant (another index type, addressing or
     mode) is made with ``dataclasses.replace``, never by assignment."""
@@ -144,6 +148,7 @@ class LatticeSource:
     half: bool = False
     smagorinsky: object = None
     macroscopic: bool = False
+    solid_field: bool = False
 
     def __post_init__(self):
         self.hip, self.fix = self.target == 'hip', self.mode == 'fix'
@@ -155,6 +160,7 @@ class LatticeSource:
         self.ff = bool(self.fm) and bool(self.force_field)
         self.of = bool(self.omega_field)
         self.mo = bool(self.macroscopic)
+        self.sf = bool(self.solid_field)
         # Guo with TRT / MRT: the force term (prefactor 1 − ω/2 with the shear rate ω, as lbmpy's Guo model) is not
         # relaxed by the collision matrix, so its adjoint sums run over g while the equilibrium's run over h
         self.sm = None if self.smagorinsky is None else float(self.smagorinsky)
@@ -198,4 +204,7 @@ class LatticeSource:
                 raise NotImplementedError(density_links_message(what))
         if self.h and (self.ff or self.of):
             raise NotImplementedError('lattice kernels for float16 pdfs: a per-cell force / relaxation-rate field is '
+                                      'not built (its adjoint would accumulate in float16)')
+        if self.h and self.sf:
+            raise NotImplementedError('lattice kernels for float16 pdfs: a per-cell solid-fraction field is '
                                       'not built (its adjoint would accumulate in float16)')

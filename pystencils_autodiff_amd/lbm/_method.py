@@ -188,6 +188,28 @@ def smagorinsky_rate(stencil, f, feq, rho, omega0, cs, compressible, omega_eff=s
     out.append(ps.Assignment(omega_eff, 2 / (1 / omega0 + R)))
     return out
 
+
+def solid_fraction_expression(solid_fraction):
+    """σ of the ``solid_fraction`` keyword: None (off) for ``None`` / ``False``, a number in [0, 1], a sympy symbol, or
+    an expression reading a field — whose fields must be scalar (one value per cell): a ``ValueError`` otherwise."""
+    if solid_fraction is None or solid_fraction is False:
+        return None
+    if isinstance(solid_fraction, ps.Field):
+        if solid_fraction.index_dimensions:
+            raise ValueError(f"solid-fraction field '{solid_fraction.name}' has an index dimension: a per-cell solid "
+                             'fraction is a scalar field (one value per cell)')
+        return solid_fraction.center
+    if isinstance(solid_fraction, bool):
+        raise ValueError('solid_fraction=True: None / False, a number in [0, 1], a sympy symbol or a field expression')
+    sigma = sp.sympify(solid_fraction)
+    for a in sigma.atoms(ps.Field.Access):
+        if a.field.index_dimensions:
+            raise ValueError(f"solid-fraction field '{a.field.name}' has an index dimension: a per-cell solid "
+                             'fraction is a scalar field (one value per cell)')
+    if sigma.is_number and not 0 <= sigma <= 1:
+        raise ValueError(f'solid_fraction={solid_fraction!r}: a number in [0, 1]')
+    return sigma
+
 # MRT moment polynomials (exponents per axis), grouped by relaxation rate: lbmpy's weighted-orthogonal MRT groups
 # (shear, bulk, third order, fourth order) [ext]; conserved moments (density, momentum) first
 _MRT_POLYS = {
@@ -257,7 +279,7 @@ def mrt_relaxation_matrices(stencil):
 def create_lb_update_rule(stencil='D2Q9', relaxation_rate=None, compressible=False, src_field=None, dst_field=None,
                           data_type='float64', layout='fzyx', kernel_type='stream_pull_collide', force_model=None,
                           force=None, method='srt', relaxation_rates=None, magic_number=sp.Rational(3, 16),
-                          zero_centered=False, smagorinsky=False):
+                          zero_centered=False, smagorinsky=False, solid_fraction=None):
     """SRT (BGK) or TRT ``stream_pull_collide`` update rule (lbmpy ``create_lb_update_rule(stencil=…,
     method='srt' | 'trt', relaxation_rate=…, compressible=…, kernel_type='stream_pull_collide')`` [ext]).
     ``relaxation_rate`` = ω: a number, or a sympy symbol left as a kernel parameter (default: the symbol ``omega``).
@@ -295,7 +317,19 @@ def create_lb_update_rule(stencil='D2Q9', relaxation_rate=None, compressible=Fal
     relaxing with ω, Guo's 1 − ω/2); constant TRT odd / MRT rates stay constant. The subexpressions ``smag_Pi_ab``,
     ``smag_N``, ``smag_q``, ``smag_R`` and ``omega_eff`` carry it (``ac.smagorinsky``: C_s; ``ac.relaxation_rate`` stays
     ω). At N = 0 the symbolic derivative of the square root is 0/0: the rule's AutoDiffOp kernels give NaN there, the
-    lattice kernels define ∂N/∂f = 0 (a uniform rest state then has the plain model's gradient)."""
+    lattice kernels define ∂N/∂f = 0 (a uniform rest state then has the plain model's gradient).
+
+    ``solid_fraction``: the partial bounce-back model of Walsh, Burwinkle and Saar — ``None`` / ``False`` off (the rule
+    as it stands, assignment for assignment), a number in [0, 1], a sympy symbol (a kernel parameter) or an expression
+    reading a scalar field (a per-cell design field, an additional input of the rule whose adjoint is accumulated over
+    the steps). With σ the value, ``c_i`` what the rule assigns without it (collision plus force term, any method) and
+    ``f_i`` the pulled pdfs (the walls' links applied, zero-centred storage with ``w_i`` added back):
+
+        dst_i = (1 − σ) c_i + σ f_ī          (ī the opposite direction; the rest population: ī = i)
+
+    (a zero-centred rule stores ``dst_i − w_i``). σ = 0 is the plain rule, σ = 1 returns every arriving population
+    reversed, and Σ_i dst_i = Σ_i f_i for every σ. The subexpression ``solid_fraction`` carries σ
+    (``ac.solid_fraction``: the expression)."""
     if kernel_type != 'stream_pull_collide':
         raise NotImplementedError("only kernel_type='stream_pull_collide' is restated")
     method = str(method).lower()
@@ -347,14 +381,23 @@ def create_lb_update_rule(stencil='D2Q9', relaxation_rate=None, compressible=Fal
         coll = [f[i] - omega * ((f[i] + f[inv[i]]) / 2 - (feq[i] + feq[inv[i]]) / 2)
                 - omega_odd * ((f[i] - f[inv[i]]) / 2 - (feq[i] - feq[inv[i]]) / 2) for i in range(st.Q)]
     back = [st.weights[i] if zero_centered else 0 for i in range(st.Q)]
-    main = [ps.Assignment(dst_field.center(i), coll[i] + (term(i, us, omega) if term else 0) - back[i])
-            for i in range(st.Q)]
+    sigma = solid_fraction_expression(solid_fraction)
+    if sigma is None:
+        main = [ps.Assignment(dst_field.center(i), coll[i] + (term(i, us, omega) if term else 0) - back[i])
+                for i in range(st.Q)]
+    else:
+        # partial bounce-back: the post-collision value blended with the arriving population of the opposite direction
+        sf = sp.Symbol('solid_fraction')
+        subs.append(ps.Assignment(sf, sigma))
+        main = [ps.Assignment(dst_field.center(i), (1 - sf) * (coll[i] + (term(i, us, omega) if term else 0))
+                              + sf * f[st.inverse_direction_index(i)] - back[i]) for i in range(st.Q)]
     ac = ps.AssignmentCollection(main, subs)
     ac.stencil = st
     ac.zero_centered = bool(zero_centered)
     ac.compressible = compressible
     ac.relaxation_rate = omega0
     ac.smagorinsky = cs
+    ac.solid_fraction = sigma
     ac.method = method
     ac.relaxation_rate_odd = omega_odd
     ac.magic_number = sp.sympify(magic_number) if method == 'trt' and relaxation_rates is None else None

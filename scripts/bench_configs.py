@@ -236,7 +236,8 @@ def run_slab(name, builder, shape, dtype, full_cells, steps=20, warmup=3):
 
 
 def run_lbm(name, stencil, shape, dtype, T=10, reps=5, compressible=False, walls=False, force_model=None,
-            force_field=False, method='srt', omega_field=False, zero_centered=False, smagorinsky=False):
+            force_field=False, method='srt', omega_field=False, zero_centered=False, smagorinsky=False,
+            solid_field=False):
     """Lattice Boltzmann time-step op (lbm.AutoDiffLatticeBoltzmannStep.create_timestep_op): T forward steps
     and the T adjoint steps, HIP events around Op.apply and backward (back-to-back applies). MLUPS = cells · T / time; algorithmic
     bytes per cell and step: forward 2q·s (read src, write dst), adjoint 3q·s (read diffdst and the recorded
@@ -246,7 +247,9 @@ def run_lbm(name, stencil, shape, dtype, T=10, reps=5, compressible=False, walls
     ``omega_field``: the relaxation rate per cell (a scalar field, an input of the op): + s forward (the ω read), + 3·s
     adjoint (the ω read, its accumulated adjoint read and written) — (2q + 1)·s and (3q + 3)·s.
     ``zero_centered``: the pdf arrays hold f − w (the float16 rows; s = 2 there).
-    ``smagorinsky``: the Smagorinsky constant C_s (the effective rate from the cell's own pdfs: no bytes of its own)."""
+    ``smagorinsky``: the Smagorinsky constant C_s (the effective rate from the cell's own pdfs: no bytes of its own).
+    ``solid_field``: the solid fraction per cell (partial bounce-back; a scalar field, an input of the op): the ω
+    field's bytes — + s forward (the σ read), + 3·s adjoint (the σ read, its accumulated adjoint read and written)."""
     import sympy as sp
     import torch
 
@@ -260,6 +263,8 @@ def run_lbm(name, stencil, shape, dtype, T=10, reps=5, compressible=False, walls
     mk = dict(method='mrt', relaxation_rates=[sp.Symbol('omega'), 1.1, 0.9, 1.2]) if method == 'mrt' else {}
     if omega_field:
         mk['relaxation_rate'] = ps.fields(f"omega_f: {dts}[{D}D]").center
+    if solid_field:
+        mk['solid_fraction'] = ps.fields(f"sigma: {dts}[{D}D]").center
     rule = lbm.create_lb_update_rule(stencil, compressible=compressible, data_type=dts, force_model=force_model,
                                      force=force, zero_centered=zero_centered, smagorinsky=smagorinsky, **mk)
     step = lbm.AutoDiffLatticeBoltzmannStep(rule, domain_size=shape, relaxation_rate=None if omega_field else 1.5,
@@ -301,6 +306,10 @@ def run_lbm(name, stencil, shape, dtype, T=10, reps=5, compressible=False, walls
         # (extras in name order: the force field F before omega_f)
         Wv = 1.5 + 0.4 * (torch.rand(tuple(shape), generator=g, device='cuda', dtype=dtype) - 0.5)
         extra += (Wv.requires_grad_(True),)
+    if solid_field:
+        # (... and sigma last)
+        Sv = 0.05 + 0.9 * torch.rand(tuple(shape), generator=g, device='cuda', dtype=dtype)
+        extra += (Sv.requires_grad_(True),)
 
     def one():
         Op.apply(x, *extra).backward(gr)
@@ -337,9 +346,10 @@ def run_lbm(name, stencil, shape, dtype, T=10, reps=5, compressible=False, walls
            'walls': walls if isinstance(walls, str) else bool(walls),
            'fwd_mlups': round(cells * T / (f_ms * 1e-3) / 1e6, 1), 'bwd_mlups': round(cells * T / (b_ms * 1e-3) / 1e6, 1),
            'fwd_ms': round(f_ms, 4), 'bwd_ms': round(b_ms, 4),
-           'fwd_GBps': round((2 * q + (D if force_field else 0) + int(omega_field)) * es * cells * T
+           'fwd_GBps': round((2 * q + (D if force_field else 0) + int(omega_field) + int(solid_field)) * es * cells * T
                              / (f_ms * 1e-3) / 1e9, 1),
-           'bwd_GBps': round((3 * q + (3 * D if force_field else 0) + 3 * int(omega_field)) * es * cells * T
+           'bwd_GBps': round((3 * q + (3 * D if force_field else 0) + 3 * int(omega_field) + 3 * int(solid_field))
+                             * es * cells * T
                              / (b_ms * 1e-3) / 1e9, 1),
            'force': (f'{force_model}, per-cell field' if force_field else force_model) if force_model else None,
            'method': method}
@@ -349,6 +359,8 @@ def run_lbm(name, stencil, shape, dtype, T=10, reps=5, compressible=False, walls
         res['omega'] = 'per-cell field'
     if smagorinsky:
         res['smagorinsky'] = smagorinsky
+    if solid_field:
+        res['solid_fraction'] = 'per-cell field'
     res['fwd_frac'] = round(res['fwd_GBps'] / PEAK, 4)
     res['bwd_frac'] = round(res['bwd_GBps'] / PEAK, 4)
     print(json.dumps(res))
@@ -465,14 +477,20 @@ def main():
             ('lbm_d2q9_f32_2048^2_smagorinsky_omega_field', 'D2Q9', (2048, 2048), torch.float32, False, 'srt', True,
              False, 0.12),
             ('lbm_d3q19_f32_192^3_smagorinsky_omega_field', 'D3Q19', (192, 192, 192), torch.float32, False, 'srt', True,
-             False, 0.12)]
+             False, 0.12),
+            # the solid fraction σ read per cell from a scalar field (partial bounce-back), its adjoint accumulated: the
+            # ω-field rows' bytes
+            ('lbm_d2q9_f32_2048^2_solid_fraction', 'D2Q9', (2048, 2048), torch.float32, False, 'srt', False, False,
+             False, True),
+            ('lbm_d3q19_f32_192^3_solid_fraction', 'D3Q19', (192, 192, 192), torch.float32, False, 'srt', False, False,
+             False, True)]
     for name, stencil, shape, dt, walls, *more in lbms:
         if only and name not in only:
             continue
         for _ in range(repeat):
             run_lbm(name, stencil, shape, dt, walls=walls, method=more[0] if more else 'srt',
                     omega_field=len(more) > 1 and more[1], zero_centered=len(more) > 2 and more[2],
-                    smagorinsky=more[3] if len(more) > 3 else False)
+                    smagorinsky=more[3] if len(more) > 3 else False, solid_field=len(more) > 4 and more[4])
 
 
 if __name__ == '__main__':
