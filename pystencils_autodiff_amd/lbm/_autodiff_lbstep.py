@@ -60,7 +60,7 @@ class SimulationResultsTensors:
 
 
 def _lattice_sweeps(step, which, launches, force=None, dforce=None, omf=None, domf=None, macro=None, sof=None,
-                    dsof=None):
+                    dsof=None, before=None):
     """The lattice kernels over ``launches`` (tensor tuples of ``LatticeKernels.forward`` / ``adjoint``) on the
     current stream: one launch plan per distinct (shapes, strides) — the first, middle and last steps — and only
     the pointers packed per launch. ``force`` (a per-cell force field): bound to every launch; ``dforce``: the
@@ -68,7 +68,8 @@ def _lattice_sweeps(step, which, launches, force=None, dforce=None, omf=None, do
     adjoint, likewise, and ``sof`` / ``dsof``: the per-cell solid fraction and its adjoint. ``macro``: per launch None,
     or the density / velocity arrays of an observed step by name
     (``LatticeKernels.operands``) — those launches run the kernels' density / velocity variant, the others the plain
-    kernels with no argument more."""
+    kernels with no argument more. ``before``: per launch None, or a callable run (enqueued) before that launch — the
+    boundary-force seeds, added into the adjoint array the launch reads."""
     K = step._lattice_kernels()
     mask = step._flag_arg()
     ids = step._ids_arg()
@@ -77,9 +78,12 @@ def _lattice_sweeps(step, which, launches, force=None, dforce=None, omf=None, do
     if which != 'adj':
         dforce = domf = dsof = None
     macro = macro or [None] * len(launches)
+    before = before or [None] * len(launches)
     if not step._gpu:
         # the C kernels on numpy arrays (both adjoint passes in one call)
-        for ts, m in zip(launches, macro):
+        for ts, m, pre in zip(launches, macro, before):
+            if pre is not None:
+                pre()
             if which == 'adj':
                 K.adjoint(*ts, om, mask, ids=ids, force=force, dforce=dforce, omf=omf, domf=domf, sof=sof, dsof=dsof,
                           **(m or {}))
@@ -94,7 +98,9 @@ def _lattice_sweeps(step, which, launches, force=None, dforce=None, omf=None, do
                                         dsof=dsof))[len(launches[0]):]
     mnames = K.table_pointer_names(which, True)[len(launches[0]) + len(mptr):]
     plans = {}
-    for ts, m in zip(launches, macro):
+    for ts, m, pre in zip(launches, macro, before):
+        if pre is not None:
+            pre()
         sig = tuple(t.stride() for t in ts) + (m is not None,)
         plan = plans.get(sig)
         if plan is None:
@@ -502,7 +508,111 @@ class AutoDiffLatticeBoltzmannStep:
         self._flag_dev = None
         self._ids_dev = None
         self._links_cached = None
+        self._force_links = {}
+        self._force_tables = {}
         self._records = None
+
+    # -- boundary force (momentum exchange) --------------------------------------------------------
+    def boundary_links(self, boundary):
+        """The links of ``boundary`` (a boundary object set on this step) as a ``BoundaryLinks``: ``cells`` — the fluid
+        cells ``x`` with ``x + c_d`` (periodic) a cell of the boundary, as C-order cell indices —, their
+        ``directions`` ``d``, sorted by (direction, cell), and ``table`` ``[Q, 2]``: ``(1 + α_d, β_d)`` of the boundary's
+        link (``_wall_force.force_table``). Built with numpy from the flags, once per flag change (and uploaded once on
+        the GPU target). ``ValueError``: a boundary never set on the step; ``NotImplementedError``: a boundary whose
+        links are not the fused form in one pdf."""
+        from ._wall_force import BoundaryLinks, boundary_links
+        if not isinstance(boundary, Boundary) or boundary not in self._boundary.conditions:
+            raise ValueError(f'boundary {boundary!r} was never set on this step (set_boundary_including_adjoint)')
+        table = self._force_table(boundary)
+        cache = self.__dict__.setdefault('_force_links', {})
+        links = cache.get(boundary)
+        if links is None:
+            cells, dirs = boundary_links(self._boundary.flags, self.method, self._boundary.conditions[boundary])
+            links = cache[boundary] = BoundaryLinks(boundary, cells, dirs, table)
+        return links
+
+    def _force_table(self, boundary):
+        """``force_table`` of a boundary set on the step, memoised until the next ``set_boundary`` (a boundary object is
+        not to be changed once set: set it again after changing, say, a ``UBB``'s velocity)."""
+        from ._wall_force import force_table
+        tabs = self.__dict__.setdefault('_force_tables', {})
+        if boundary not in tabs:
+            tabs[boundary] = force_table(boundary, self._boundary.adjoints[self._boundary.conditions[boundary]],
+                                         self._bc_method, getattr(self._update_rule, 'zero_centered', False))
+        return tabs[boundary]
+
+    def _wall_force_kernels(self):
+        from ._wall_force import WallForceKernels
+        k = self.__dict__.get('_wall_force')
+        if k is None:
+            k = self._wall_force = WallForceKernels(self.method, self.pdf_field.dtype.numpy_dtype, self._target)
+        return k
+
+    def _force_spec(self, spec):
+        """``boundary_force_outputs`` as a list of ``(boundary, k)``: a boundary, a ``(boundary, k)`` pair or a list
+        of those, ``k ≥ 1`` (default 1); every boundary checked (``boundary_links``)."""
+        if isinstance(spec, Boundary) or (isinstance(spec, tuple) and len(spec) == 2 and isinstance(spec[0], Boundary)
+                                          and not isinstance(spec[1], Boundary)):
+            spec = [spec]
+        out = []
+        for e in spec:
+            b, k = (e, 1) if isinstance(e, Boundary) else e
+            if isinstance(k, (float, bool)) or int(k) < 1:
+                raise ValueError(f'boundary_force_outputs: (boundary, k) with an int k >= 1, got k = {k!r}')
+            self.boundary_links(b)
+            out.append((b, int(k)))
+        return out
+
+    def create_boundary_force_op(self, boundary, backend='torch_native', block_cap=None):
+        """A ``torch.autograd.Function`` for the force the fluid exerts on ``boundary`` by momentum exchange
+        (lbmpy's ``force_on_boundary``): ``Op.apply(pdfs)`` with a state ``pdfs`` ``[*domain, q]`` of the step's dtype
+        (post-collision pdfs — what the time-step op takes and returns; any strides) returns ``force [D]`` in the
+        compute type (float32 for float16 / float32 pdfs, float64 for float64):
+
+            F = Σ_links c_d·((1 + α_d)·f_d(x) + β_d)       over the links (x, d) of ``boundary`` (``boundary_links``)
+
+        Its backward returns a zeroed array of ``pdfs``' shape plus ``(1 + α_d)·c_d·dF`` on the links. The link list
+        is taken at every apply (``set_boundary`` between two applies changes it). ``block_cap``: the most workgroups
+        of the HIP reduction's first stage (``_wall_force.DEFAULT_BLOCK_CAP``)."""
+        if str(backend).lower() not in ('torch_native', 'torch'):
+            raise NotImplementedError(f"backend '{backend}': only the torch backends are built")
+        self.boundary_links(boundary)               # the refusals, at creation
+        torch = _torch()
+        step, gpu = self, self._gpu
+        K = self._wall_force_kernels()
+        pdt = np.dtype(self.pdf_field.dtype.numpy_dtype)
+        cdt = getattr(torch, K.cdtype.name)
+
+        class LbmBoundaryForce(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, pdfs):
+                links = step.boundary_links(boundary)
+                if tuple(pdfs.shape) != tuple(step.domain_size) + (step.method.Q,) or \
+                        pdfs.dtype != getattr(torch, pdt.name):
+                    raise TypeError(f'{LbmBoundaryForce.__name__}.apply(pdfs): pdfs [*{step.domain_size}, '
+                                    f'{step.method.Q}] of {pdt.name}, got {tuple(pdfs.shape)} {pdfs.dtype}')
+                ctx.links = links
+                x = pdfs.detach()
+                # (the gradient's layout: the input's, kept as a tensor without memory)
+                ctx.like = torch.empty_strided(x.shape, x.stride(), dtype=x.dtype, device='meta')
+                if gpu:
+                    return K.force(x, links, cap=block_cap)
+                return torch.from_numpy(K.force(x.cpu().numpy(), links))
+
+            @staticmethod
+            def backward(ctx, dF):
+                links, like = ctx.links, ctx.like           # (small, kept: a retained graph runs this again)
+                g = torch.zeros_like(like, device=dF.device if gpu else 'cpu')
+                d = dF.detach().to(cdt).contiguous()
+                if gpu:
+                    K.adjoint(g, links, d)
+                else:
+                    K.adjoint(g.numpy(), links, d.cpu().numpy())
+                return g
+
+        LbmBoundaryForce.lb_step = self
+        LbmBoundaryForce.boundary = boundary
+        return LbmBoundaryForce
 
     def _flag_arg(self):
         """The cells' neighbour masks for the wall kernels (computed once per flag change), None without walls."""
@@ -717,7 +827,7 @@ class AutoDiffLatticeBoltzmannStep:
 
     # -- torch ops ---------------------------------------------------------------------------------
     def create_timestep_op(self, num_time_steps, input_field_to_tensor_dict=None, backend='torch_native',
-                           macroscopic_outputs=None):
+                           macroscopic_outputs=None, boundary_force_outputs=None):
         """A ``torch.autograd.Function`` for ``num_time_steps`` steps: ``Op.apply(pdfs)`` with the interior
         pdfs (``[*domain_size, q]``) returns the pdfs after the steps; its backward runs the adjoint steps
         in reverse over the recorded states (``_autodiff_lbstep.py:189-247``; the reference's
@@ -726,7 +836,12 @@ class AutoDiffLatticeBoltzmannStep:
         ``macroscopic_outputs``: ``True`` or an int ``k ≥ 1`` — the op returns ``(pdfs, rho, vel)`` with the density
         ``rho [n, *domain]`` and the velocity ``vel [n, *domain, D]`` of the states k, 2k, …, nk, ``n = T // k``
         (state t: the output of step t), written by the lattice kernels that compute those states, and its backward
-        takes their gradients too (``_observed_timestep_op``)."""
+        takes their gradients too (``_observed_timestep_op``).
+
+        ``boundary_force_outputs``: a boundary object set on the step, a ``(boundary, k)`` pair (``k ≥ 1``, default 1)
+        or a list of those — the op returns its usual outputs followed by one ``force [n, D]`` per entry: the
+        momentum-exchange force on that boundary (``create_boundary_force_op``) of the states k, 2k, …, nk,
+        ``n = T // k``, computed on the recorded states in place; its backward takes their gradients too."""
         if str(backend).lower() not in ('torch_native', 'torch'):
             raise NotImplementedError(f"backend '{backend}': only the torch backends are built")
         extras = list(self._additional_fields)
@@ -734,7 +849,12 @@ class AutoDiffLatticeBoltzmannStep:
         unknown = [getattr(f, 'name', f) for f in (input_field_to_tensor_dict or {}) if getattr(f, 'name', f) not in known]
         if unknown:
             raise ValueError(f'input fields {unknown} are not read by the update rule (inputs: {sorted(known)})')
-        if macroscopic_outputs is not None and macroscopic_outputs is not False:
+        if macroscopic_outputs is False:
+            macroscopic_outputs = None
+        if boundary_force_outputs is not None:
+            return self._observed_timestep_op(int(num_time_steps), macroscopic_outputs, extras,
+                                              self._force_spec(boundary_force_outputs))
+        if macroscopic_outputs is not None:
             return self._observed_timestep_op(int(num_time_steps), macroscopic_outputs, extras)
         torch = _torch()
         step = self
@@ -842,7 +962,7 @@ class AutoDiffLatticeBoltzmannStep:
         LbmTimesteps.lb_step = self
         return LbmTimesteps
 
-    def _observed_timestep_op(self, T, every, extras):
+    def _observed_timestep_op(self, T, every, extras, forces=()):
         """The time-step op that also returns the density and the velocity of every ``every``-th state
         (``create_timestep_op(macroscopic_outputs=…)``): ``Op.apply(pdfs, *extras)`` → ``(pdfs, rho, vel)``.
 
@@ -852,19 +972,29 @@ class AutoDiffLatticeBoltzmannStep:
         ``rho [n, *domain]`` and ``vel [n, *domain, D]`` (stored component-first, a permuted view) are one
         uninitialised allocation each. Backward takes ``(grad_pdfs, grad_rho, grad_vel)``, any of them None (both
         observable gradients None: the plain adjoint kernels throughout); an observable's gradient in the layout the
-        op returned is read in place, any other gets one copy."""
+        op returned is read in place, any other gets one copy.
+
+        ``forces`` (``create_timestep_op(boundary_force_outputs=…)``, a list of ``(boundary, k)``): one more output
+        ``force [T // k, D]`` per entry, after the others; ``every`` None: no density / velocity outputs. The force
+        launches run after the sweeps on the recorded states (and on the output state when T is observed). Backward:
+        before the adjoint launch that reads the adjoint of state t, the seeds of the forces observed at t are added
+        into that array on the boundary's links (the caller's ``grad``: copied once first); a force gradient that is
+        None launches nothing."""
         if self._lattice is None:
             raise NotImplementedError(
-                'macroscopic_outputs: the density / velocity outputs are written by the lattice kernels, and this '
-                'rule is not on the lattice schedule (it runs on the AutoDiffOp kernels: a rule not made by '
+                'macroscopic_outputs / boundary_force_outputs: the density / velocity outputs are written by the lattice '
+                'kernels, and this rule is not on the lattice schedule (it runs on the AutoDiffOp kernels: a rule not made by '
                 'create_lb_update_rule, time-constant or other additional fields, a symbolic rate or force the '
                 'lattice kernels do not take, or PSAD_LBM_LATTICE=0)')
-        if isinstance(every, float) or int(every) < 1:
+        if every is not None and (isinstance(every, float) or int(every) < 1):
             raise ValueError(f'macroscopic_outputs: True or an int k >= 1, got {every!r}')
         torch = _torch()
-        step, k, gpu = self, int(every), self._gpu
-        n, D, dims = T // k, len(self.domain_size), list(self.domain_size)
+        observed = every is not None
+        step, k, gpu = self, int(every) if observed else 1, self._gpu
+        n, D, dims = T // k if observed else 0, len(self.domain_size), list(self.domain_size)
         slot = {j * k - 1: j - 1 for j in range(1, n + 1)}          # launch t (its output: state t + 1) → slot
+        forces = list(forces)
+        WF = self._wall_force_kernels() if forces else None
         pdt = np.dtype(self.pdf_field.dtype.numpy_dtype)
         cdt = getattr(torch, 'float64' if pdt == np.float64 else 'float32')     # the kernels' compute type
         view = (0,) + tuple(range(2, D + 2)) + (1,)                 # [n, D, *domain] → [n, *domain, D]
@@ -903,8 +1033,8 @@ class AutoDiffLatticeBoltzmannStep:
                 else:
                     states = [np.asarray(x0.cpu().numpy(), dtype=pdt)] + [step._alloc(zero=False) for _ in range(T)]
                     dev = 'cpu'
-                rho = torch.empty([n] + dims, dtype=cdt, device=dev)
-                vel = torch.empty([n, D] + dims, dtype=cdt, device=dev).permute(*view)
+                rho = torch.empty([n] + dims, dtype=cdt, device=dev) if observed else None
+                vel = torch.empty([n, D] + dims, dtype=cdt, device=dev).permute(*view) if observed else None
                 macro = [None] * T
                 for t, j in slot.items():
                     macro[t] = dict(rho_out=arrays(rho[j]), vel_out=arrays(vel[j]))
@@ -917,20 +1047,46 @@ class AutoDiffLatticeBoltzmannStep:
                 # forward and backward raises)
                 ctx.save_for_backward(pdfs if ctx.input_is_state0 else None, rho, vel)
                 ctx.set_materialize_grads(False)
-                return out, rho, vel
+                # the boundary forces of the observed states: launches on the states where they lie (no copies); the
+                # link lists as they are now, kept for the backward
+                fout, ctx.force_links = [], []
+                for b, kf in forces:
+                    links = step.boundary_links(b)
+                    ctx.force_links.append(links)
+                    Fo = torch.empty([T // kf, D], dtype=cdt, device=dev)
+                    for j in range(T // kf):
+                        WF.force(states[(j + 1) * kf], links, out=arrays(Fo[j]))
+                    fout.append(Fo)
+                return (out, rho, vel, *fout) if observed else (out, *fout)
 
             @staticmethod
-            def backward(ctx, grad, grad_rho, grad_vel):
+            def backward(ctx, grad, *more):
+                grad_rho, grad_vel = more[:2] if observed else (None, None)
+                grad_forces = more[2:] if observed else more
                 ex = ctx.extras
                 ctx.extras = None
                 x0, rho, vel = ctx.saved_tensors
-                rho, vel = rho.detach(), vel.detach()
+                if observed:
+                    rho, vel = rho.detach(), vel.detach()
+                # state t → [(links, dF)] of the forces observed there whose gradient arrived
+                seeds = {}
+                for (b, kf), links, gF in zip(forces, ctx.force_links, grad_forces):
+                    if gF is None or links.n == 0:
+                        continue
+                    gF = gF.detach().to(cdt).contiguous()
+                    for j in range(T // kf):
+                        seeds.setdefault((j + 1) * kf, []).append((links, arrays(gF[j] if gpu else gF[j].cpu())))
+                ctx.force_links = None
                 if grad is None:
                     g = step._alloc(zero=True)
                 elif gpu:
                     g = grad if step._lattice_input_ok(grad) else step._as_layout(grad)
                 else:
                     g = np.asarray(grad.detach().cpu().numpy(), dtype=pdt)
+                if T in seeds and grad is not None and (
+                        g.data_ptr() == grad.data_ptr() if gpu else np.shares_memory(g, grad.detach().cpu().numpy())):
+                    # the seed of F(s_T) goes into the adjoint of state T: not into the caller's tensor
+                    g = g.clone() if gpu else g.copy()
                 records = list(ctx.records)
                 if ctx.input_is_state0:
                     x0 = x0.detach()
@@ -939,13 +1095,16 @@ class AutoDiffLatticeBoltzmannStep:
                 ping = step._internal_states(min(2, T - 1)) if gpu else \
                     [step._alloc(zero=False) for _ in range(min(2, T - 1))]
                 out = step._alloc(zero=False)
-                cur, launches, macro = g, [], []
+                cur, launches, macro, before = g, [], [], []
                 seeded = grad_rho is not None or grad_vel is not None
                 if seeded:
                     drho, dvel = as_returned(grad_rho, rho), as_returned(grad_vel, vel)
                 for t in reversed(range(T)):
                     nxt = out if t == 0 else ping[(T - 1 - t) % 2]
                     launches.append((records[t], cur, nxt))
+                    # (this launch reads ``cur``, the adjoint of state t + 1)
+                    before.append(None if t + 1 not in seeds else
+                                  (lambda a=cur, ls=seeds[t + 1]: [WF.adjoint(a, links, dF) for links, dF in ls]))
                     j = slot.get(t) if seeded else None
                     macro.append(None if j is None else dict(rho_out=arrays(rho[j]), vel_out=arrays(vel[j]),
                                                              drho=arrays(drho[j]), dvel=arrays(dvel[j])))
@@ -955,7 +1114,8 @@ class AutoDiffLatticeBoltzmannStep:
                 dex = {f.name: (torch.zeros_like if gpu else np.zeros_like)(ex[f.name]) for f in extras}
                 _lattice_sweeps(step, 'adj', launches, F, None if F is None else dex[step._force_field.name],
                                 W, None if W is None else dex[step._omega_field.name], macro=macro,
-                                sof=S, dsof=None if S is None else dex[step._solid_field.name])
+                                sof=S, dsof=None if S is None else dex[step._solid_field.name],
+                                before=before if seeds else None)
                 if not gpu:
                     return (torch.from_numpy(out), *[torch.from_numpy(dex[f.name]) for f in extras])
                 return (out, *[dex[f.name] for f in extras])
@@ -963,6 +1123,8 @@ class AutoDiffLatticeBoltzmannStep:
         LbmTimestepsObserved.num_time_steps = T
         LbmTimestepsObserved.lb_step = self
         LbmTimestepsObserved.observed_states = tuple(j * k for j in range(1, n + 1))
+        LbmTimestepsObserved.boundary_force_states = tuple(tuple(j * kf for j in range(1, T // kf + 1))
+                                                           for _, kf in forces)
         return LbmTimestepsObserved
 
     def _field_layout(self, f, t):
@@ -982,13 +1144,17 @@ class AutoDiffLatticeBoltzmannStep:
 
     def create_end_to_end_op(self, num_time_steps, velocity_input_tensor, density_input_tensor,
                              additional_fields_to_tensor_map=None, force_input_tensor=None, backend='torch_native',
-                             num_times_steps_without_save=0, macroscopic_outputs=False, **kernel_compilation_kwargs):
+                             num_times_steps_without_save=0, macroscopic_outputs=False, boundary_force_outputs=None,
+                             **kernel_compilation_kwargs):
         """Equilibrium from (ρ, u) → ``num_time_steps`` steps → (ρ, u), differentiable end to end
         (``_autodiff_lbstep.py:310-334``, there TensorFlow only): the setter op, the time-step ops in groups of
         ``num_times_steps_without_save + 1`` steps, the getter op, evaluated on the given tensors (torch
         autograd records the chain). Returns ``SimulationResultsTensors``. ``macroscopic_outputs``: every group is
         observed at its end (``create_timestep_op(group, macroscopic_outputs=group)``) and the result also carries
-        ``density_trajectory`` ``[groups, *domain]`` and ``velocity_trajectory`` ``[groups, *domain, D]``."""
+        ``density_trajectory`` ``[groups, *domain]`` and ``velocity_trajectory`` ``[groups, *domain, D]``.
+        ``boundary_force_outputs`` (a boundary or a list of boundaries set on the step): the force on each at every
+        group's end, ``boundary_force_trajectory`` ``[groups, D]`` (a list of those for a list; a ``(boundary, k)`` pair is
+        accepted with k = 1 only)."""
         if str(backend).lower() not in ('torch_native', 'torch'):
             raise NotImplementedError(f"backend '{backend}': only the torch backends are built")
         from ._method import force_is_field
@@ -1010,15 +1176,29 @@ class AutoDiffLatticeBoltzmannStep:
                              'getter': self.create_macroscopic_getter_op(backend, **kernel_compilation_kwargs)}
         ops = self._e2e_ops
         group = int(num_times_steps_without_save) + 1
+        bodies = None
+        if boundary_force_outputs is not None:
+            # (a boundary, a (boundary, 1) pair or a list of those, as the time-step op parses them; every group is
+            # observed at its end, so another k has no meaning here)
+            spec = self._force_spec(boundary_force_outputs)
+            if any(k != 1 for _, k in spec):
+                raise ValueError('create_end_to_end_op(boundary_force_outputs=…): boundaries, not (boundary, k) pairs '
+                                 'with k > 1 — the force is taken at the end of every group of '
+                                 'num_times_steps_without_save + 1 steps')
+            bodies = [b for b, _ in spec]
         step_op = self.create_timestep_op(group, backend=backend,
-                                          macroscopic_outputs=group if macroscopic_outputs else None)
+                                          macroscopic_outputs=group if macroscopic_outputs else None,
+                                          boundary_force_outputs=None if bodies is None else [(b, group) for b in bodies])
         (input_pdf,) = ops['setter'].apply(density_input_tensor, velocity_input_tensor)
         out = input_pdf
         trajectory = []
+        force_trajectory = []
         for _ in range(int(num_time_steps) // group):
-            if macroscopic_outputs:
+            if macroscopic_outputs or bodies is not None:
                 out, *observed = step_op.apply(out, *xs)
-                trajectory.append(observed)
+                if macroscopic_outputs:
+                    trajectory.append(observed[:2])
+                force_trajectory.append(observed[2 if macroscopic_outputs else 0:])
             else:
                 out = step_op.apply(out, *xs)
         rho, vel = self._apply_getter(ops['getter'], out, given)
@@ -1027,6 +1207,12 @@ class AutoDiffLatticeBoltzmannStep:
             torch = _torch()
             result.density_trajectory = torch.cat([r for r, _ in trajectory]) if trajectory else None
             result.velocity_trajectory = torch.cat([v for _, v in trajectory]) if trajectory else None
+        if bodies is not None:
+            torch = _torch()
+            per_body = [torch.cat([fs[i] for fs in force_trajectory]) if force_trajectory else None
+                        for i in range(len(bodies))]
+            result.boundary_force_trajectory = per_body if isinstance(boundary_force_outputs, list) or \
+                len(per_body) > 1 else per_body[0]
         return result
 
     def _macroscopic_fields(self):

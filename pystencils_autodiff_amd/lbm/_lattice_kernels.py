@@ -40,7 +40,8 @@ from ._lattice_source import FIX_BIT, FIX_BLOCK, SELF_BIT  # noqa: F401 (the bit
 from ._lattice_source import ARRAYS, LatticeSource, emit, kernel_args, link_programs, struct_format
 from ._lattice_source.args import CELLS, EXTENT, KERNELS, POINTER, RATE, REACH, STRIDE
 
-__all__ = ['LatticeKernels', 'LaunchPlan', 'lattice_strides', 'row_interleaved_empty', 'neighbour_mask']
+__all__ = ['LatticeKernels', 'LaunchPlan', 'lattice_strides', 'row_interleaved_empty', 'neighbour_mask',
+           'addressing_mode']
 
 
 def fix_cells(flags, stencil, program_ids, programs=None):
@@ -134,6 +135,24 @@ def row_interleaved_empty(domain, Q, dtype, device):
     dims = list(domain)
     base = torch.empty(dims[:-1] + [Q, dims[-1]], dtype=dtype, device=device)
     return base.transpose(-1, -2)
+
+
+def _reach(t):
+    """Elements from the tensor's base to its last element (+1)."""
+    return sum(abs(int(s)) * (int(n) - 1) for s, n in zip(t.stride(), t.shape)) + 1
+
+
+def addressing_mode(tensors):
+    """``(idx, addr)`` of a launch on these pdf tensors, by the largest reach among them: ``'buf'`` below 2³¹
+    bytes (2 GiB) and ``'ptr'`` from there on (or with a negative stride, or ``PSAD_LBM_ADDR=ptr``); ``'int'``
+    up to 2³¹ − 2 elements and ``'long long'`` from 2³¹ − 1. (The lattice kernels' and the boundary-force kernels'.)"""
+    reach = max(_reach(t) for t in tensors)
+    idx = 'int' if reach < 2 ** 31 - 1 else 'long long'
+    esz = tensors[0].element_size()
+    addr = 'buf' if reach * esz < 2 ** 31 and all(min(t.stride()) >= 0 for t in tensors) else 'ptr'
+    if os.environ.get('PSAD_LBM_ADDR') == 'ptr':       # A/B of the addressing modes (probes)
+        addr = 'ptr'
+    return idx, addr
 
 
 class LatticeKernels:
@@ -322,22 +341,13 @@ class LatticeKernels:
                 vals.append(float(omega) if a.kind == RATE else int(ops['cells'].numel()))
         return vals
 
-    @staticmethod
-    def _reach(t):
-        """Elements from the tensor's base to its last element (+1)."""
-        return sum(abs(int(s)) * (int(n) - 1) for s, n in zip(t.stride(), t.shape)) + 1
+    _reach = staticmethod(_reach)
 
     def _mode(self, tensors):
         """``(idx, addr)`` of a launch on these pdf tensors, by the largest reach among them: ``'buf'`` below 2³¹
         bytes (2 GiB) and ``'ptr'`` from there on (or with a negative stride, or ``PSAD_LBM_ADDR=ptr``); ``'int'``
-        up to 2³¹ − 2 elements and ``'long long'`` from 2³¹ − 1."""
-        reach = max(self._reach(t) for t in tensors)
-        idx = 'int' if reach < 2 ** 31 - 1 else 'long long'
-        esz = tensors[0].element_size()
-        addr = 'buf' if reach * esz < 2 ** 31 and all(min(t.stride()) >= 0 for t in tensors) else 'ptr'
-        if os.environ.get('PSAD_LBM_ADDR') == 'ptr':       # A/B of the addressing modes (probes)
-            addr = 'ptr'
-        return idx, addr
+        up to 2³¹ − 2 elements and ``'long long'`` from 2³¹ − 1 (``addressing_mode``)."""
+        return addressing_mode(tensors)
 
     def _launch_mode(self, tensors, force=None, dforce=None, omf=None, domf=None, *more, sof=None, dsof=None):
         """``(idx, addr)`` of a ``plan()`` launch: ``_mode`` of the pdf tensors; the force, the ω and the σ field (and

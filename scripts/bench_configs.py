@@ -237,7 +237,7 @@ def run_slab(name, builder, shape, dtype, full_cells, steps=20, warmup=3):
 
 def run_lbm(name, stencil, shape, dtype, T=10, reps=5, compressible=False, walls=False, force_model=None,
             force_field=False, method='srt', omega_field=False, zero_centered=False, smagorinsky=False,
-            solid_field=False):
+            solid_field=False, body=False, boundary_force=None):
     """Lattice Boltzmann time-step op (lbm.AutoDiffLatticeBoltzmannStep.create_timestep_op): T forward steps
     and the T adjoint steps, HIP events around Op.apply and backward (back-to-back applies). MLUPS = cells · T / time; algorithmic
     bytes per cell and step: forward 2q·s (read src, write dst), adjoint 3q·s (read diffdst and the recorded
@@ -249,7 +249,11 @@ def run_lbm(name, stencil, shape, dtype, T=10, reps=5, compressible=False, walls
     ``zero_centered``: the pdf arrays hold f − w (the float16 rows; s = 2 there).
     ``smagorinsky``: the Smagorinsky constant C_s (the effective rate from the cell's own pdfs: no bytes of its own).
     ``solid_field``: the solid fraction per cell (partial bounce-back; a scalar field, an input of the op): the ω
-    field's bytes — + s forward (the σ read), + 3·s adjoint (the σ read, its accumulated adjoint read and written)."""
+    field's bytes — + s forward (the σ read), + 3·s adjoint (the σ read, its accumulated adjoint read and written).
+    ``body``: a no-slip cylinder (2-D, diameter 256) or sphere (3-D, diameter 48) in the middle of the lattice
+    (``_body_mask``). ``boundary_force``: k — the op also returns the momentum-exchange force on the body of every k-th
+    state (``boundary_force_outputs=(body, k)``) and the backward takes its gradient: two small launches per observed
+    state forward, one backward, over the body's links only (no bytes per cell)."""
     import sympy as sp
     import torch
 
@@ -282,7 +286,11 @@ def run_lbm(name, stencil, shape, dtype, T=10, reps=5, compressible=False, walls
         # ... driven by FixedDensity inlet / outlet planes at the ends of axis 0 (link programs)
         step.set_boundary_including_adjoint(lbm.FixedDensity(1.01, name='inlet'), lbm.make_slice[0, 1:-1])
         step.set_boundary_including_adjoint(lbm.FixedDensity(0.99, name='outlet'), lbm.make_slice[-1, 1:-1])
-    Op = step.create_timestep_op(T)
+    body_obj = None
+    if body:
+        body_obj = lbm.NoSlip('body')
+        step.set_boundary_including_adjoint(body_obj, mask_array=_body_mask(shape))
+    Op = step.create_timestep_op(T, boundary_force_outputs=(body_obj, int(boundary_force)) if boundary_force else None)
     q = rule.stencil.Q
     g = torch.Generator(device='cuda').manual_seed(0)
     f0 = (torch.full(tuple(shape) + (q,), 1.0 / q, device='cuda', dtype=torch.float64) *
@@ -311,8 +319,16 @@ def run_lbm(name, stencil, shape, dtype, T=10, reps=5, compressible=False, walls
         Sv = 0.05 + 0.9 * torch.rand(tuple(shape), generator=g, device='cuda', dtype=dtype)
         extra += (Sv.requires_grad_(True),)
 
+    gF = torch.ones((T // int(boundary_force), D), device='cuda', dtype=torch.float32) if boundary_force else None
+
+    def backward(out):
+        if boundary_force:
+            torch.autograd.backward(list(out), [gr, gF])
+        else:
+            out.backward(gr)
+
     def one():
-        Op.apply(x, *extra).backward(gr)
+        backward(Op.apply(x, *extra))
         x.grad = None
         for e in extra:
             e.grad = None
@@ -325,7 +341,7 @@ def run_lbm(name, stencil, shape, dtype, T=10, reps=5, compressible=False, walls
         e0.record()
         out = Op.apply(x, *extra)
         e1.record()
-        out.backward(gr)
+        backward(out)
         e2.record()
         x.grad = None
         for e in extra:
@@ -361,11 +377,104 @@ def run_lbm(name, stencil, shape, dtype, T=10, reps=5, compressible=False, walls
         res['smagorinsky'] = smagorinsky
     if solid_field:
         res['solid_fraction'] = 'per-cell field'
+    if body:
+        res['body'] = {'kind': 'cylinder d=256' if D == 2 else 'sphere d=48', 'links': step.boundary_links(body_obj).n}
+    if boundary_force:
+        res['boundary_force_every'] = int(boundary_force)
     res['fwd_frac'] = round(res['fwd_GBps'] / PEAK, 4)
     res['bwd_frac'] = round(res['bwd_GBps'] / PEAK, 4)
     print(json.dumps(res))
     sys.stdout.flush()
     del x, out, gr, f0, Op
+    torch.cuda.empty_cache()
+
+
+def _body_mask(shape):
+    """A cylinder of diameter 256 (2-D) or a sphere of diameter 48 (3-D) in the middle of the lattice."""
+    import numpy as np
+    r = 128.0 if len(shape) == 2 else 24.0
+    grids = np.meshgrid(*[np.arange(n) + 0.5 - n / 2 for n in shape], indexing='ij', sparse=True)
+    return sum(g * g for g in grids) <= r * r
+
+
+def run_lbm_force(name, stencil, shape, dtype, reps=200):
+    """The boundary-force op alone (``create_boundary_force_op``) on a no-slip channel with the body of ``_body_mask``:
+    forward and backward, HIP events around ``reps`` back-to-back applies (and backwards), per call; beside it the torch
+    restatement a user of the time-step op alone has to write (Q − 1 rolled masks and masked products over whole
+    states), on the same state. Bytes: what each has to touch at least — the kernels the link list (cell index,
+    direction byte) and one pdf per link (the adjoint reads and writes it), the restatement Q − 1 component planes and
+    mask planes forward and a state-sized gradient backward. The kernels' own times are in a kernel trace
+    (profiles/lbm_boundary_force_kernel_trace.jsonl); the op's time here includes the host's enqueue."""
+    import torch
+
+    from pystencils_autodiff_amd import lbm
+    D = len(shape)
+    dts = str(dtype).replace('torch.', '')
+    rule = lbm.create_lb_update_rule(stencil, data_type=dts)
+    step = lbm.AutoDiffLatticeBoltzmannStep(rule, domain_size=shape, relaxation_rate=1.5, target='gpu')
+    step.set_boundary_including_adjoint(lbm.NoSlip(), lbm.make_slice[:, 0])
+    step.set_boundary_including_adjoint(lbm.NoSlip(), lbm.make_slice[:, -1])
+    body = lbm.NoSlip('body')
+    mask = _body_mask(shape)
+    step.set_boundary_including_adjoint(body, mask_array=mask)
+    q = rule.stencil.Q
+    g = torch.Generator(device='cuda').manual_seed(0)
+    x = step.empty_pdfs()
+    x.copy_(torch.full(tuple(shape) + (q,), 1.0 / q, device='cuda') *
+            (1 + 0.01 * torch.rand(tuple(shape) + (q,), generator=g, device='cuda')))
+    x.requires_grad_(True)
+    Op = step.create_boundary_force_op(body)
+    wall = torch.from_numpy(mask).cuda()
+    fluid = torch.from_numpy(step.boundary_handling.flags == 0).cuda()
+    dirs = [tuple(int(v) for v in c) for c in rule.stencil.directions]
+
+    def restated(f):
+        F = [0.0] * D
+        for d, c in enumerate(dirs):
+            if any(c):
+                tot = (2 * f[..., d] * (fluid & torch.roll(wall, tuple(-v for v in c), tuple(range(D))))).sum()
+                for a, ca in enumerate(c):
+                    if ca:
+                        F[a] = F[a] + ca * tot
+        return torch.stack(F)
+    dF = torch.tensor([1.0, -0.5, 0.25][:D], device='cuda')
+    ref, got = restated(x.detach()), Op.apply(x.detach())
+    err = float((ref - got).abs().max() / ref.abs().max())
+    times = {}
+    for what, fn, n in (('op', Op.apply, reps), ('torch', restated, max(3, reps // 20))):
+        for _ in range(3):
+            fn(x).backward(dF)
+            x.grad = None
+        fw, bw = [], []
+        for _ in range(5):
+            e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+            e0.record()
+            outs = [fn(x) for _ in range(n)]
+            e1.record()
+            for o in outs:
+                o.backward(dF)
+                x.grad = None
+            e2.record()
+            torch.cuda.synchronize()
+            fw.append(e0.elapsed_time(e1) / n)
+            bw.append(e1.elapsed_time(e2) / n)
+        times[what] = (sorted(fw)[2], sorted(bw)[2])
+    cells = 1
+    for n_ in shape:
+        cells *= n_
+    es = x.element_size()
+    nl = step.boundary_links(body).n
+    nb = step._wall_force_kernels().blocks(nl)
+    print(json.dumps({
+        'config': name, 'shape': list(shape), 'dtype': dts, 'links': nl, 'blocks': nb,
+        'op_fwd_us': round(times['op'][0] * 1e3, 2), 'op_bwd_us': round(times['op'][1] * 1e3, 2),
+        'torch_fwd_us': round(times['torch'][0] * 1e3, 2), 'torch_bwd_us': round(times['torch'][1] * 1e3, 2),
+        'op_fwd_bytes': nl * (4 + 1 + es) + 2 * nb * D * 8 + D * 4, 'op_bwd_bytes': nl * (4 + 1 + 2 * es) + D * 4,
+        'op_bwd_zero_fill_bytes': cells * q * es,
+        'torch_fwd_bytes_min': (q - 1) * cells * (es + 2), 'torch_bwd_bytes_min': (q - 1) * cells * (es + 1) + cells * q * es,
+        'restatement_rel_diff': err}))
+    sys.stdout.flush()
+    del x, Op
     torch.cuda.empty_cache()
 
 
@@ -491,6 +600,19 @@ def main():
             run_lbm(name, stencil, shape, dt, walls=walls, method=more[0] if more else 'srt',
                     omega_field=len(more) > 1 and more[1], zero_centered=len(more) > 2 and more[2],
                     smagorinsky=more[3] if len(more) > 3 else False, solid_field=len(more) > 4 and more[4])
+    # the momentum-exchange force on a body in the channel: the plain op with the body, the op that also returns the
+    # force of every state (and takes its gradient), and the force op alone beside its torch restatement
+    for stencil, shape, tag in (('D2Q9', (2048, 2048), 'lbm_d2q9_f32_2048^2_channel_cylinder'),
+                                ('D3Q19', (192, 192, 192), 'lbm_d3q19_f32_192^3_channel_sphere')):
+        for name, k in ((tag, None), (tag + '_force', 1)):
+            if only and name not in only:
+                continue
+            for _ in range(repeat):
+                run_lbm(name, stencil, shape, torch.float32, walls=True, body=True, boundary_force=k)
+        name = tag.replace('lbm_', 'lbm_force_op_').replace('_channel', '')
+        if not only or name in only:
+            for _ in range(repeat):
+                run_lbm_force(name, stencil, shape, torch.float32)
 
 
 if __name__ == '__main__':
