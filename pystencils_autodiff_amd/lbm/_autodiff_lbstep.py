@@ -29,15 +29,14 @@ adjoint kernel written for the lattice, any pdf strides, the op's internal state
 ``_autodiff_lbstep.py:162-187``; half-way bounce-back fused into the pull, obstacle cells keep their state).
 Other rules run on the ``AutoDiffOp`` kernels (periodic, no walls).
 """
-import os
-
 import numpy as np
 import sympy as sp
 
 from .. import ps
 from ..autodiff import AutoDiffOp
 from ._lattice_kernels import LatticeKernels, fix_cells, neighbour_mask
-from ._lattice_source import density_links_message, link_rows
+from ._lattice_rule import lattice_rule
+from ._lattice_source import CELL_FIELDS, density_links_message, link_rows
 from ._method import LBStencil
 from .boundaries import (AdjointBoundaryCondition, AdjointNoSlip, Boundary, BoundaryHandling, LBMethodView,  # noqa: F401
                          NoSlip, link_form)
@@ -59,14 +58,12 @@ class SimulationResultsTensors:
         self.output_velocity_tensor = output_velocity_tensor
 
 
-def _lattice_sweeps(step, which, launches, force=None, dforce=None, omf=None, domf=None, macro=None, sof=None,
-                    dsof=None, before=None):
+def _lattice_sweeps(step, which, launches, fields=None, macro=None, before=None):
     """The lattice kernels over ``launches`` (tensor tuples of ``LatticeKernels.forward`` / ``adjoint``) on the
     current stream: one launch plan per distinct (shapes, strides) — the first, middle and last steps — and only
-    the pointers packed per launch. ``force`` (a per-cell force field): bound to every launch; ``dforce``: the
-    adjoint launches add their force adjoints into it. ``omf`` / ``domf``: the per-cell relaxation rate and its
-    adjoint, likewise, and ``sof`` / ``dsof``: the per-cell solid fraction and its adjoint. ``macro``: per launch None,
-    or the density / velocity arrays of an observed step by name
+    the pointers packed per launch. ``fields``: the per-cell fields (``step._field_args``: kind → (array, adjoint)),
+    bound to every launch; the adjoint launches add their share into each field's adjoint array. ``macro``: per launch
+    None, or the density / velocity arrays of an observed step by name
     (``LatticeKernels.operands``) — those launches run the kernels' density / velocity variant, the others the plain
     kernels with no argument more. ``before``: per launch None, or a callable run (enqueued) before that launch — the
     boundary-force seeds, added into the adjoint array the launch reads."""
@@ -75,8 +72,6 @@ def _lattice_sweeps(step, which, launches, force=None, dforce=None, omf=None, do
     ids = step._ids_arg()
     cells = step._cells_arg()
     om = step._omega_of()
-    if which != 'adj':
-        dforce = domf = dsof = None
     macro = macro or [None] * len(launches)
     before = before or [None] * len(launches)
     if not step._gpu:
@@ -84,18 +79,13 @@ def _lattice_sweeps(step, which, launches, force=None, dforce=None, omf=None, do
         for ts, m, pre in zip(launches, macro, before):
             if pre is not None:
                 pre()
-            if which == 'adj':
-                K.adjoint(*ts, om, mask, ids=ids, force=force, dforce=dforce, omf=omf, domf=domf, sof=sof, dsof=dsof,
-                          **(m or {}))
-            else:
-                K.forward(*ts, om, mask, ids=ids, force=force, omf=omf, sof=sof, **(m or {}))
+            K.run(which, list(ts), om, mask, ids, fields, m)
         return
     stream = _torch()._C._cuda_getCurrentRawStream(launches[0][0].device.index)
     rho = K.rho_buffer(launches[0][0]) if which == 'adj' and K.link_pass else None
     # once: the launches differ in their pdf arrays (the leading pointer slots) and, the observed ones, in the
     # density / velocity arrays (the trailing ones)
-    mptr = K.pointers(which, K.operands((), mask, ids, force, dforce, omf, domf, rho, sof=sof,
-                                        dsof=dsof))[len(launches[0]):]
+    mptr = K.pointers(which, K.operands((), mask, ids, fields, rho))[len(launches[0]):]
     mnames = K.table_pointer_names(which, True)[len(launches[0]) + len(mptr):]
     plans = {}
     for ts, m, pre in zip(launches, macro, before):
@@ -104,52 +94,14 @@ def _lattice_sweeps(step, which, launches, force=None, dforce=None, omf=None, do
         sig = tuple(t.stride() for t in ts) + (m is not None,)
         plan = plans.get(sig)
         if plan is None:
-            plan = plans[sig] = K.plan(which, list(ts), mask, om, ids, force, dforce, omf=omf, domf=domf, macro=m,
-                                       sof=sof, dsof=dsof)
+            plan = plans[sig] = K.plan(which, list(ts), mask, om, ids, fields, macro=m)
         plan(tuple(t.data_ptr() for t in ts) + mptr +
              (tuple(0 if m.get(n) is None else m[n].data_ptr() for n in mnames) if m else ()), stream, om)
         # link-program walls (HIP): the fix-up kernels over the cells next to them
-        K.fix_launch(which, list(ts), mask, om, ids, force, dforce, cells, stream, omf, domf, m, sof, dsof)
+        K.fix_launch(which, list(ts), mask, om, ids, fields, cells, stream, m)
         if rho is not None:
             # the second pass of density-weighted walls (and, on the CPU, link programs) on this launch's output
             K.rho_pass(ts[2], mask, rho, stream)
-
-
-def _plain_force_field(force, D):
-    """The force FIELD when the rule's force is exactly ``F(x)[a]`` per axis a (one field of D components read at
-    the cell itself), else None."""
-    if force is None:
-        return None
-    comps = [sp.sympify(v) for v in force]
-    if len(comps) != D or not all(isinstance(c, ps.Field.Access) for c in comps):
-        return None
-    fields = {c.field for c in comps}
-    if len(fields) != 1:
-        return None
-    (F,) = fields
-    if F.index_dimensions != 1 or int(F.index_shape[0]) != D:
-        return None
-    for a, c in enumerate(comps):
-        if tuple(int(o) for o in c.offsets) != (0,) * D or tuple(int(i) for i in c.index) != (a,):
-            return None
-    return F
-
-
-def _plain_omega_field(rate, D, dtype):
-    """The relaxation-rate FIELD when the rule's ω is exactly ``w(x)``: a scalar field (no index dimension) of the
-    pdf dtype read at the cell itself, else None."""
-    if not isinstance(rate, ps.Field.Access):
-        return None
-    w = rate.field
-    if w.index_dimensions != 0 or w.spatial_dimensions != D or tuple(int(o) for o in rate.offsets) != (0,) * D:
-        return None
-    return w if np.dtype(w.dtype.numpy_dtype) == np.dtype(dtype) else None
-
-
-def _plain_solid_field(sigma, D, dtype):
-    """The solid-fraction FIELD when the rule's σ is exactly ``s(x)``: a scalar field (no index dimension) of the pdf
-    dtype read at the cell itself, else None."""
-    return _plain_omega_field(sigma, D, dtype)
 
 
 def _guess_src_dst_field_from_update_rule(update_rule, src_hint, dst_hint):
@@ -261,90 +213,20 @@ class AutoDiffLatticeBoltzmannStep:
         self._device = device
         self._arrays = {}
         self._records = None
-        # the lattice schedule for the rules of create_lb_update_rule (SRT, stream_pull_collide); walls need it
-        # a per-cell rate read as w(x) (a scalar field of the pdf dtype at the cell itself): the lattice kernels take
-        # the field as an array and accumulate its adjoint (their scalar ω argument is then unused); any other rate
-        # expression that reads a field (1/(3 ν(x) + 1/2), an offset read, another dtype) runs on the AutoDiffOp kernels
-        self._omega_field = _plain_omega_field(rr, src.spatial_dimensions, src.dtype.numpy_dtype)
-        if self._omega_field is not None:
-            self._omega_of = lambda: 0.0
-        elif rate_fields:
-            self._omega_of = None
-        else:
-            self._omega_of = (lambda: float(self.kernel_params[rr.name])) if isinstance(rr, sp.Symbol) else \
-                ((lambda v=rr: float(v)) if rr is not None else None)
-        # (PSAD_LBM_LATTICE=0: the AutoDiffOp kernels instead — tests of that path, A/B probes)
-        force = getattr(update_rule, 'force', None)
-        # a per-cell force read as F(x)[a] (the field's centre, component a, for every axis): the lattice kernels
-        # take the field as an array and accumulate its adjoint; any other force expression runs on the AutoDiffOp
-        # kernels
-        self._force_field = _plain_force_field(force, src.spatial_dimensions)
-        if self._force_field is not None:
-            self._lattice_force = (getattr(update_rule, 'force_model', None), None)
-        else:
-            self._lattice_force = (getattr(update_rule, 'force_model', None),
-                                   None if force is None else tuple(float(v) for v in force)) \
-                if force is None or all(sp.sympify(v).is_number for v in force) else None
-        # a per-cell solid fraction read as s(x) (a scalar field of the pdf dtype at the cell itself): the lattice
-        # kernels take the field as an array and accumulate its adjoint; any other σ (a number, a symbol, an offset
-        # read, another dtype) runs on the AutoDiffOp kernels
-        sigma = getattr(update_rule, 'solid_fraction', None)
-        self._solid_field = None if sigma is None else \
-            _plain_solid_field(sigma, src.spatial_dimensions, src.dtype.numpy_dtype)
-        solid_ok = sigma is None or self._solid_field is not None
-        extras_ok = set(self._additional_fields) == {f for f in (self._omega_field, self._force_field,
-                                                                 self._solid_field) if f is not None}
-        # TRT: the odd rate from the magic number (a function of the ω argument) or a constant
-        self._lattice_trt = None
-        trt_ok = True
-        if getattr(update_rule, 'method', 'srt') == 'trt':
-            if getattr(update_rule, 'magic_number', None) is not None:
-                self._lattice_trt = ('magic', float(update_rule.magic_number))
-            elif sp.sympify(update_rule.relaxation_rate_odd).is_number:
-                self._lattice_trt = ('rate', float(update_rule.relaxation_rate_odd))
-            else:
-                trt_ok = False                      # a symbolic odd rate: the AutoDiffOp kernels
-        # MRT: the relaxation matrix A = ω P_ω + C (groups relaxing with the rule's ω / with constant rates)
-        self._lattice_mrt = None
-        if getattr(update_rule, 'method', 'srt') == 'mrt':
-            from ._method import MRT_GROUPS, mrt_relaxation_matrices
-            P = mrt_relaxation_matrices(update_rule.stencil)
-            Qn = update_rule.stencil.Q
-            Pw = [[0.0] * Qn for _ in range(Qn)]
-            Cm = [[0.0] * Qn for _ in range(Qn)]
-            om = sp.sympify(update_rule.relaxation_rate)
-            for grp in MRT_GROUPS:
-                r = sp.sympify(update_rule.mrt_rates[grp])
-                if r == om:
-                    tgt, scale = Pw, 1.0
-                elif r.is_number:
-                    tgt, scale = Cm, float(r)
-                else:
-                    trt_ok = False                  # a symbolic rate other than ω: the AutoDiffOp kernels
-                    break
-                for i in range(Qn):
-                    for k in range(Qn):
-                        tgt[i][k] += scale * float(P[grp][i][k])
-            else:
-                self._lattice_mrt = (Pw, Cm)
-        # Smagorinsky: a numeric C_s is a constant of the lattice kernels; a symbolic one, float16 pdfs or a per-cell
-        # force field (its adjoint would need ∂ω_eff/∂F) run on the AutoDiffOp kernels
-        cs = getattr(update_rule, 'smagorinsky', None)
-        self._lattice_smagorinsky = float(cs) if cs is not None and sp.sympify(cs).is_number else None
-        smag_ok = cs is None or (self._lattice_smagorinsky is not None and self._force_field is None
-                                 and np.dtype(src.dtype.numpy_dtype) != np.float16)
-        self._lattice = {} if (getattr(update_rule, 'stencil', None) is not None and not time_constant_fields
-                               and self._lattice_force is not None and smag_ok
-                               and os.environ.get('PSAD_LBM_LATTICE', '1') != '0'
-                               and extras_ok and solid_ok and trt_ok and self._omega_of is not None
-                               and np.dtype(src.dtype.numpy_dtype) in (np.float16, np.float32, np.float64)
-                               # (float16 pdfs with a force / ω / σ field: the AutoDiffOp kernels — the lattice
-                               # kernels would accumulate the field's adjoint over the steps in float16)
-                               and (np.dtype(src.dtype.numpy_dtype) != np.float16 or
-                                    (self._force_field is None and self._omega_field is None
-                                     and self._solid_field is None))
-                               and (self._force_field is None or
-                                    self._force_field.dtype.numpy_dtype == src.dtype.numpy_dtype)) else None
+        # the lattice schedule for the rules of create_lb_update_rule (``lattice_rule``: which rules, and what their
+        # kernels are built from); walls need it. ``_lattice``: the step's LatticeKernels by wall set, None for a rule
+        # that runs on the AutoDiffOp kernels
+        self._lattice_rule = rule = lattice_rule(update_rule, src, time_constant_fields)
+        self._lattice = None if rule is None else {}
+        # the per-cell fields the lattice kernels take as arrays, by kind (``CELL_FIELDS``) and by name
+        self._cell_fields = {f.kind: None if rule is None else rule.fields[f.kind] for f in CELL_FIELDS}
+        self._force_field, self._omega_field, self._solid_field = (self._cell_fields[k] for k in
+                                                                   ('force', 'omega', 'solid'))
+        self._lattice_mrt = None if rule is None else rule.mrt
+        # the kernels' scalar ω argument (unused with an ω field)
+        how, value = (None, None) if rule is None else rule.rate
+        self._omega_of = {None: None, 'field': lambda: 0.0, 'param': lambda: float(self.kernel_params[value]),
+                          'number': lambda: float(value)}[how]
         self._boundary = BoundaryHandling(self.domain_size, on_change=self._flags_changed)
         # the lb_method the boundaries see: the stencil plus the rule's compressibility (FixedDensity reads it)
         self._bc_method = LBMethodView(self.method, getattr(update_rule, 'compressible', False))
@@ -677,16 +559,16 @@ class AutoDiffLatticeBoltzmannStep:
     def _lattice_kernels(self):
         walls = self._boundary.has_walls
         links, programs = self._link_data()
-        key = (walls, links, programs, self._lattice_smagorinsky, self._solid_field is not None)
+        key = (walls, links, programs)
         k = self._lattice.get(key)
         if k is None:
+            rule = self._lattice_rule
             k = self._lattice[key] = LatticeKernels(
                 self.method, getattr(self._update_rule, 'compressible', False), self.pdf_field.dtype.numpy_dtype,
-                walls, self._target, links, *self._lattice_force, force_field=self._force_field is not None,
-                trt=self._lattice_trt, programs=programs, mrt=self._lattice_mrt,
-                omega_field=self._omega_field is not None,
-                zero_centered=getattr(self._update_rule, 'zero_centered', False),
-                smagorinsky=self._lattice_smagorinsky, solid_field=self._solid_field is not None)
+                walls, self._target, links, rule.force_model, rule.force, force_field=self._force_field is not None,
+                trt=rule.trt, programs=programs, mrt=rule.mrt, omega_field=self._omega_field is not None,
+                zero_centered=getattr(self._update_rule, 'zero_centered', False), smagorinsky=rule.smagorinsky,
+                solid_field=self._solid_field is not None)
         return k
 
     # -- kernels -----------------------------------------------------------------------------------
@@ -698,9 +580,8 @@ class AutoDiffLatticeBoltzmannStep:
 
     def _fwd(self, src, dst, extra):
         if self._lattice is not None:
-            return self._lattice_kernels().forward(src, dst, self._omega_of(), self._flag_arg(), ids=self._ids_arg(),
-                                                   force=self._force_arg(extra), cells=self._cells_arg(),
-                                                   omf=self._omega_arg(extra), sof=self._solid_arg(extra))
+            return self._lattice_kernels().run('fwd', [src, dst], self._omega_of(), self._flag_arg(), self._ids_arg(),
+                                               self._field_args(extra), cells=self._cells_arg())
         kf = self._forward_kernel()
         kf(**{self._pdf_arr_name: src, self._tmp_arr_name: dst}, **extra, **self.kernel_params)
 
@@ -719,62 +600,56 @@ class AutoDiffLatticeBoltzmannStep:
                                                function_name=f'LBM_forward_{tgt}', target=tgt)
         return self._forward_only.compile()
 
-    def _force_arg(self, extra):
-        """The per-cell force array of the lattice kernels (None without a force field)."""
-        if self._force_field is None:
-            return None
-        try:
-            return extra[self._force_field.name]
-        except (KeyError, TypeError):
-            raise ValueError(f"the update rule reads the force field '{self._force_field.name}': pass its array "
-                             "(extra={name: array})") from None
+    def _field_args(self, extra, adjoints=None):
+        """The per-cell fields of a lattice launch (``LatticeKernels.run``): kind → (the field's array from ``extra``,
+        by the field's name; its adjoint array from ``adjoints``, by kind, or None) for the fields the rule reads."""
+        fields = {}
+        for row in CELL_FIELDS:
+            f = self._cell_fields[row.kind]
+            if f is None:
+                continue
+            try:
+                fields[row.kind] = (extra[f.name], (adjoints or {}).get(row.kind))
+            except (KeyError, TypeError):
+                raise ValueError(f"the update rule reads the {row.what} '{f.name}': pass its array "
+                                 "(extra={name: array})") from None
+        return fields
 
-    def _omega_arg(self, extra):
-        """The per-cell relaxation-rate array of the lattice kernels (None without an ω field)."""
-        if self._omega_field is None:
-            return None
-        try:
-            return extra[self._omega_field.name]
-        except (KeyError, TypeError):
-            raise ValueError(f"the update rule reads the relaxation-rate field '{self._omega_field.name}': pass its "
-                             "array (extra={name: array})") from None
+    def _field_adjoints(self, extra_adj):
+        """Kind → the adjoint array (accumulated into) of every per-cell field the rule reads, from ``extra_adj`` by
+        the field's adjoint name."""
+        adjoints = {}
+        for row in CELL_FIELDS:
+            if self._cell_fields[row.kind] is not None:
+                name = self._adjoint_name(self._cell_fields[row.kind])
+                if name not in (extra_adj or {}):
+                    raise ValueError(f"the {row.what}'s adjoint '{name}' needs an array (extra_adj), accumulated into")
+                adjoints[row.kind] = extra_adj[name]
+        return adjoints
 
-    def _solid_arg(self, extra):
-        """The per-cell solid-fraction array of the lattice kernels (None without a σ field)."""
-        if self._solid_field is None:
-            return None
-        try:
-            return extra[self._solid_field.name]
-        except (KeyError, TypeError):
-            raise ValueError(f"the update rule reads the solid-fraction field '{self._solid_field.name}': pass its "
-                             "array (extra={name: array})") from None
+    def _zeroed_field_adjoints(self, ex, extras, zeros_like):
+        """For the adjoint sweep of a time-step op: ``(dex, fields)`` — by name a zeroed array like each additional
+        input of ``ex`` (every step's adjoint launch adds its share into it) and the sweep's per-cell fields with
+        those arrays as their adjoints."""
+        dex = {f.name: zeros_like(ex[f.name]) for f in extras}
+        return dex, self._field_args(ex, {k: dex[f.name] for k, f in self._cell_fields.items() if f is not None})
+
+    def _adjoint_launches(self, records, g, ping, out):
+        """The T adjoint launches ``(state t, adjoint of state t + 1, adjoint of state t)``, t = T − 1 … 0: the adjoints
+        of states T − 1 … 1 alternate between the arrays ``ping``; the gradient (the adjoint of state 0) is ``out``."""
+        T = len(records)
+        cur, launches = g, []
+        for t in reversed(range(T)):
+            nxt = out if t == 0 else ping[(T - 1 - t) % 2]
+            launches.append((records[t], cur, nxt))
+            cur = nxt
+        return launches
 
     def _bwd(self, src, diffdst, diffsrc, extra, extra_adj):
         if self._lattice is not None:
-            dsof = None
-            if self._solid_field is not None:
-                name = self._adjoint_name(self._solid_field)
-                if name not in (extra_adj or {}):
-                    raise ValueError(f"the solid-fraction field's adjoint '{name}' needs an array (extra_adj), "
-                                     'accumulated into')
-                dsof = extra_adj[name]
-            domf = None
-            if self._omega_field is not None:
-                name = self._adjoint_name(self._omega_field)
-                if name not in (extra_adj or {}):
-                    raise ValueError(f"the relaxation-rate field's adjoint '{name}' needs an array (extra_adj), "
-                                     'accumulated into')
-                domf = extra_adj[name]
-            dforce = None
-            if self._force_field is not None:
-                name = self._adjoint_name(self._force_field)
-                if name not in (extra_adj or {}):
-                    raise ValueError(f"the force field's adjoint '{name}' needs an array (extra_adj), accumulated into")
-                dforce = extra_adj[name]
-            return self._lattice_kernels().adjoint(src, diffdst, diffsrc, self._omega_of(), self._flag_arg(),
-                                                   ids=self._ids_arg(), force=self._force_arg(extra), dforce=dforce,
-                                                   cells=self._cells_arg(), omf=self._omega_arg(extra), domf=domf,
-                                                   sof=self._solid_arg(extra), dsof=dsof)
+            fields = self._field_args(extra, self._field_adjoints(extra_adj))
+            return self._lattice_kernels().run('adj', [src, diffdst, diffsrc], self._omega_of(), self._flag_arg(),
+                                               self._ids_arg(), fields, cells=self._cells_arg())
         _, kb = self._kernels()
         kb(**{self._pdf_arr_name: src, 'diff' + self._tmp_arr_name: diffdst, 'diff' + self._pdf_arr_name: diffsrc},
            **extra, **extra_adj, **self.kernel_params)
@@ -887,8 +762,7 @@ class AutoDiffLatticeBoltzmannStep:
                 x0 = x0 if lattice and step._lattice_input_ok(x0) else step._as_layout(x0)
                 if lattice:
                     states = [x0] + step._internal_states(T - 1) + [step._alloc(zero=False)]
-                    _lattice_sweeps(step, 'fwd', [(states[t], states[t + 1]) for t in range(T)],
-                                    step._force_arg(ex), omf=step._omega_arg(ex), sof=step._solid_arg(ex))
+                    _lattice_sweeps(step, 'fwd', [(states[t], states[t + 1]) for t in range(T)], step._field_args(ex))
                 else:
                     states = [x0]
                     for t in range(T):
@@ -929,23 +803,15 @@ class AutoDiffLatticeBoltzmannStep:
                 if lattice:
                     # adjoints of states T-1 .. 1 alternate between two row-interleaved arrays; the gradient
                     # (adjoint of state 0) leaves in the field's layout
-                    ping = step._internal_states(min(2, T - 1))
                     out = step._alloc(zero=False)
-                    cur, launches = g, []
-                    for t in reversed(range(T)):
-                        nxt = out if t == 0 else ping[(T - 1 - t) % 2]
-                        launches.append((records[t], cur, nxt))
-                        cur = nxt
+                    launches = step._adjoint_launches(records, g, step._internal_states(min(2, T - 1)), out)
                     if not extras:
                         _lattice_sweeps(step, 'adj', launches)
                         return out
                     # the force / ω / σ adjoint: every step's adjoint launch adds its share into one array, zeroed
                     # once
-                    F, W, S = step._force_arg(ex), step._omega_arg(ex), step._solid_arg(ex)
-                    dex = {f.name: torch.zeros_like(ex[f.name]) for f in extras}
-                    _lattice_sweeps(step, 'adj', launches, F, None if F is None else dex[step._force_field.name],
-                                    W, None if W is None else dex[step._omega_field.name],
-                                    sof=S, dsof=None if S is None else dex[step._solid_field.name])
+                    dex, fields = step._zeroed_field_adjoints(ex, extras, torch.zeros_like)
+                    _lattice_sweeps(step, 'adj', launches, fields)
                     return (out, *[dex[f.name] for f in extras])
                 cur = g
                 acc = {n: torch.zeros_like(x) for n, x in ex.items()}
@@ -1038,8 +904,8 @@ class AutoDiffLatticeBoltzmannStep:
                 macro = [None] * T
                 for t, j in slot.items():
                     macro[t] = dict(rho_out=arrays(rho[j]), vel_out=arrays(vel[j]))
-                _lattice_sweeps(step, 'fwd', [(states[t], states[t + 1]) for t in range(T)], step._force_arg(ex),
-                                omf=step._omega_arg(ex), macro=macro, sof=step._solid_arg(ex))
+                _lattice_sweeps(step, 'fwd', [(states[t], states[t + 1]) for t in range(T)], step._field_args(ex),
+                                macro=macro)
                 ctx.input_is_state0 = gpu and states[0].data_ptr() == pdfs.data_ptr()
                 ctx.records = states[1:-1] if ctx.input_is_state0 else states[:-1]
                 out = states[-1] if gpu else torch.from_numpy(states[-1])
@@ -1095,27 +961,20 @@ class AutoDiffLatticeBoltzmannStep:
                 ping = step._internal_states(min(2, T - 1)) if gpu else \
                     [step._alloc(zero=False) for _ in range(min(2, T - 1))]
                 out = step._alloc(zero=False)
-                cur, launches, macro, before = g, [], [], []
+                launches, macro, before = step._adjoint_launches(records, g, ping, out), [], []
                 seeded = grad_rho is not None or grad_vel is not None
                 if seeded:
                     drho, dvel = as_returned(grad_rho, rho), as_returned(grad_vel, vel)
-                for t in reversed(range(T)):
-                    nxt = out if t == 0 else ping[(T - 1 - t) % 2]
-                    launches.append((records[t], cur, nxt))
+                for t, (_, cur, _) in zip(reversed(range(T)), launches):
                     # (this launch reads ``cur``, the adjoint of state t + 1)
                     before.append(None if t + 1 not in seeds else
                                   (lambda a=cur, ls=seeds[t + 1]: [WF.adjoint(a, links, dF) for links, dF in ls]))
                     j = slot.get(t) if seeded else None
                     macro.append(None if j is None else dict(rho_out=arrays(rho[j]), vel_out=arrays(vel[j]),
                                                              drho=arrays(drho[j]), dvel=arrays(dvel[j])))
-                    cur = nxt
                 # the force / ω / σ adjoint: every step's adjoint launch adds its share into one array, zeroed once
-                F, W, S = step._force_arg(ex), step._omega_arg(ex), step._solid_arg(ex)
-                dex = {f.name: (torch.zeros_like if gpu else np.zeros_like)(ex[f.name]) for f in extras}
-                _lattice_sweeps(step, 'adj', launches, F, None if F is None else dex[step._force_field.name],
-                                W, None if W is None else dex[step._omega_field.name], macro=macro,
-                                sof=S, dsof=None if S is None else dex[step._solid_field.name],
-                                before=before if seeds else None)
+                dex, fields = step._zeroed_field_adjoints(ex, extras, torch.zeros_like if gpu else np.zeros_like)
+                _lattice_sweeps(step, 'adj', launches, fields, macro=macro, before=before if seeds else None)
                 if not gpu:
                     return (torch.from_numpy(out), *[torch.from_numpy(dex[f.name]) for f in extras])
                 return (out, *[dex[f.name] for f in extras])

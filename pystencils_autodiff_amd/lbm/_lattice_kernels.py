@@ -27,7 +27,9 @@ What this schedule does differently:
 One source is printed for both targets (``_lattice_source``): a HIP kernel (one thread per cell, wave64 along x)
 compiled by hiprtc, and a C loop nest (``use_cuda=False`` / ``target='cpu'``) compiled by gcc. This module holds the
 host side: masks and cell lists, compiling, argument buffers and launches. Every argument buffer is laid out by the
-printer's own table of the kernel's arguments (``_lattice_source.args.kernel_args``) and filled by name.
+printer's own table of the kernel's arguments (``_lattice_source.args.kernel_args``) and filled by name. The per-cell
+fields of a launch (force, relaxation rate, solid fraction: the rows of ``_lattice_source.fields.CELL_FIELDS``) travel
+as one bundle ``{kind: (array, adjoint or None)}`` (``field_pair``); only ``forward`` / ``adjoint`` take them as keywords.
 """
 import ctypes
 import dataclasses
@@ -37,7 +39,7 @@ import struct
 import numpy as np
 
 from ._lattice_source import FIX_BIT, FIX_BLOCK, SELF_BIT  # noqa: F401 (the bits: re-exported)
-from ._lattice_source import ARRAYS, LatticeSource, emit, kernel_args, link_programs, struct_format
+from ._lattice_source import ARRAYS, CELL_FIELDS, LatticeSource, emit, kernel_args, link_programs, struct_format
 from ._lattice_source.args import CELLS, EXTENT, KERNELS, POINTER, RATE, REACH, STRIDE
 
 __all__ = ['LatticeKernels', 'LaunchPlan', 'lattice_strides', 'row_interleaved_empty', 'neighbour_mask',
@@ -104,20 +106,25 @@ def lattice_strides(t, D):
     return (st[D],) + (0,) * (3 - D) + tuple(st[:D])
 
 
+def field_pair(fields, kind):
+    """``(array, adjoint)`` of the per-cell field ``kind`` in a launch's bundle ``fields`` (``{kind: (array, adjoint or
+    None)}`` over the kinds of ``CELL_FIELDS``, or None for no field at all): ``(None, None)`` for one not given."""
+    return (fields or {}).get(kind, (None, None))
+
+
 def _stride_values(ops, D):
-    """name → value of every stride argument the operands ``ops`` give: ``{p}_{q,z,y,x}`` of the pdf arrays,
-    ``f_{c,z,y,x}`` of the force field, ``w_{z,y,x}`` of the ω field, ``p_{z,y,x}`` of the σ field (2-D: the z strides
+    """name → value of every stride argument the operands ``ops`` give: ``{p}_{q,z,y,x}`` of the pdf arrays and the
+    per-cell fields' by their rows of ``CELL_FIELDS`` (``f_{c,z,y,x}``, ``w_{z,y,x}``, ``p_{z,y,x}``; 2-D: the z strides
     are 0)."""
     v = {}
-    for p, t in [(p, ops.get(name)) for p, name in ARRAYS.items()] + [('f', ops.get('force'))]:
+    for p, name in ARRAYS.items():
+        if ops.get(name) is not None:
+            v.update(zip((f'{p}_q', f'{p}_z', f'{p}_y', f'{p}_x'), lattice_strides(ops[name], D)))
+    for f in CELL_FIELDS:
+        t = ops.get(f.operand)
         if t is not None:
-            v.update(zip((f'{p}_c' if p == 'f' else f'{p}_q', f'{p}_z', f'{p}_y', f'{p}_x'), lattice_strides(t, D)))
-    if ops.get('omf') is not None:
-        sw = _element_strides(ops['omf'])
-        v.update(zip(('w_z', 'w_y', 'w_x'), [0] * (3 - len(sw)) + sw))
-    if ops.get('sigf') is not None:
-        sp_ = _element_strides(ops['sigf'])
-        v.update(zip(('p_z', 'p_y', 'p_x'), [0] * (3 - len(sp_)) + sp_))
+            st = _element_strides(t)
+            v.update(zip(f.strides, lattice_strides(t, D) if f.vector else [0] * (3 - len(st)) + st))
     # the density / velocity outputs and their seeds (one set of strides: the seeds have the outputs' layout)
     rho = ops.get('rho_out') if ops.get('rho_out') is not None else ops.get('drho')
     vel = ops.get('vel_out') if ops.get('vel_out') is not None else ops.get('dvel')
@@ -287,15 +294,16 @@ class LatticeKernels:
             raise ValueError('the periodic lattice needs at least 2 cells per axis')
 
     @staticmethod
-    def operands(tensors, mask, ids, force=None, dforce=None, omf=None, domf=None, scratch=None, macro=None,
-                 sof=None, dsof=None):
+    def operands(tensors, mask, ids, fields=None, scratch=None, macro=None):
         """Argument name → operand (torch tensors, or numpy arrays on the C path; None: not given) of ``lbm_fwd``
-        (``tensors``: src, dst) or ``lbm_adj`` / ``lbm_adj_fix`` (src, g, out). ``macro``: None, or by name the arrays
-        of the density / velocity variant (``rho_out``, ``vel_out``, ``drho``, ``dvel``). ``sof`` / ``dsof``: the solid
-        fraction and its adjoint."""
-        return dict(zip(('src', 'dst') if len(tensors) == 2 else ('src', 'g', 'out'), tensors), nbmask=mask,
-                    wallid=ids, force=force, dforce=dforce, omf=omf, domega=domf, sigf=sof, dsolid=dsof, rho_adj=scratch,
-                    **(macro or {}))
+        (``tensors``: src, dst) or ``lbm_adj`` / ``lbm_adj_fix`` (src, g, out). ``fields``: the launch's per-cell fields
+        (``field_pair``), under the names their rows of ``CELL_FIELDS`` print. ``macro``: None, or by name the arrays
+        of the density / velocity variant (``rho_out``, ``vel_out``, ``drho``, ``dvel``)."""
+        ops = dict(zip(('src', 'dst') if len(tensors) == 2 else ('src', 'g', 'out'), tensors), nbmask=mask,
+                   wallid=ids, rho_adj=scratch, **(macro or {}))
+        for f in CELL_FIELDS if fields else ():
+            ops[f.operand], ops[f.adjoint] = field_pair(fields, f.kind)
+        return ops
 
     def pointers(self, kernel, ops, macro=False):
         """The pointer slots a launch of ``lbm_{kernel}`` patches, in the table's order, from the operands ``ops``
@@ -349,56 +357,51 @@ class LatticeKernels:
         up to 2³¹ − 2 elements and ``'long long'`` from 2³¹ − 1 (``addressing_mode``)."""
         return addressing_mode(tensors)
 
-    def _launch_mode(self, tensors, force=None, dforce=None, omf=None, domf=None, *more, sof=None, dsof=None):
-        """``(idx, addr)`` of a ``plan()`` launch: ``_mode`` of the pdf tensors; the force, the ω and the σ field (and
-        their adjoints) are read through plain pointers with IDX offsets, so a far-reaching one widens ``idx`` alone."""
+    def _launch_mode(self, tensors, fields=None, more=()):
+        """``(idx, addr)`` of a ``plan()`` launch: ``_mode`` of the pdf tensors; the per-cell fields and their adjoints
+        (``fields``) and the arrays ``more`` are read through plain pointers with IDX offsets, so a far-reaching one
+        widens ``idx`` alone."""
         idx, addr = self._mode(tensors)
-        if max([self._reach(t) for t in (force, dforce, omf, domf, sof, dsof) + more if t is not None],
-               default=0) >= 2 ** 31 - 1:
+        plain = [t for f in CELL_FIELDS for t in field_pair(fields, f.kind)] + list(more)
+        if max([self._reach(t) for t in plain if t is not None], default=0) >= 2 ** 31 - 1:
             idx = 'long long'
         return idx, addr
 
-    def _field_check(self, kind, shape, field, adjoint, which, xp_tensor=True):
-        """A per-cell field ``kind`` — 'force': ``[*domain, D]``, 'omega' (the relaxation rate) / 'solid' (the solid
-        fraction): ``[*domain]`` — and, for the adjoint kernel, its accumulated adjoint: both of the pdf dtype,
-        ``adjoint`` with the strides of ``field``;
-        none where the kernels take no such field."""
+    def _field_check(self, shape, fields, which, xp_tensor=True):
+        """The per-cell fields of a launch, each by its row of ``CELL_FIELDS`` — ``[*domain, D]`` or ``[*domain]`` —
+        and, for the adjoint kernel, its accumulated adjoint: both of the pdf dtype, ``adjoint`` with the strides of
+        ``field``; none where the kernels take no such field."""
         D = self.stencil.D
-        on, want = (self.force_field, tuple(shape[:D]) + (D,)) if kind == 'force' else \
-            (self.omega_field if kind == 'omega' else self.solid_field, tuple(shape[:D]))
-        what, kernels, name, short = ('force field', 'force-field', 'force', 'force') if kind == 'force' else \
-            ('relaxation-rate field', 'ω-field', 'relaxation-rate field', 'relaxation-rate') if kind == 'omega' else \
-            ('solid-fraction field', 'σ-field', 'solid-fraction field', 'solid-fraction')
-        need = [field] + ([adjoint] if which == 'adj' else [])
-        if not on:
-            if field is not None or adjoint is not None:
-                raise ValueError(f'these lattice kernels take no {what}')
-            return
-        if any(t is None for t in need):
-            raise ValueError(f'the {kernels} lattice kernels need the {name}'
-                             f'{" and its adjoint" if which == "adj" else ""}')
-        for t in need:
-            if tuple(t.shape) != want:
-                raise ValueError(f'{what} of shape {tuple(t.shape)}: expected {want}')
-            if (t.dtype != self.dtype) if not xp_tensor else (str(t.dtype).split('.')[-1] != self.dtype.name):
-                raise ValueError(f'{what} dtype {t.dtype}: expected {self.dtype}')
-        if which == 'adj' and tuple(adjoint.stride() if xp_tensor else adjoint.strides) != \
-                tuple(field.stride() if xp_tensor else field.strides):
-            raise ValueError(f'the {short} adjoint must have the strides of the {name}')
+        for f in CELL_FIELDS:
+            field, adjoint = field_pair(fields, f.kind)
+            want = tuple(shape[:D]) + ((D,) if f.vector else ())
+            need = [field] + ([adjoint] if which == 'adj' else [])
+            if not getattr(self.spec, f.flag):
+                if field is not None or adjoint is not None:
+                    raise ValueError(f'these lattice kernels take no {f.what}')
+                continue
+            if any(t is None for t in need):
+                raise ValueError(f'the {f.kernels} lattice kernels need the {f.name}'
+                                 f'{" and its adjoint" if which == "adj" else ""}')
+            for t in need:
+                if tuple(t.shape) != want:
+                    raise ValueError(f'{f.what} of shape {tuple(t.shape)}: expected {want}')
+                if (t.dtype != self.dtype) if not xp_tensor else (str(t.dtype).split('.')[-1] != self.dtype.name):
+                    raise ValueError(f'{f.what} dtype {t.dtype}: expected {self.dtype}')
+            if which == 'adj' and tuple(adjoint.stride() if xp_tensor else adjoint.strides) != \
+                    tuple(field.stride() if xp_tensor else field.strides):
+                raise ValueError(f'the {f.short} adjoint must have the strides of the {f.name}')
 
-    def plan(self, which, tensors, mask, omega, ids=None, force=None, dforce=None, fix=None, omf=None, domf=None,
-             macro=None, sof=None, dsof=None):
+    def plan(self, which, tensors, mask, omega, ids=None, fields=None, fix=None, macro=None):
         """The launch of ``which`` ('fwd' / 'adj') on tensors of these shapes, strides, dtype and device (with or
         without walls): a ``LaunchPlan`` whose pointer slots and relaxation rate are patched per launch — the
         time-step op launches T of them per apply. ω is not part of the key (a trained or scheduled rate reuses the
         plan); the plan is built with the first ω it sees. ``fix``: (cells,) — the fix-up kernel of ``which`` over
-        the listed cells (int32 cell indices). ``macro``: the arrays of the density / velocity variant (``operands``),
-        whose pointers every launch patches too. ``sof`` / ``dsof``: the per-cell solid fraction and its adjoint."""
+        the listed cells (int32 cell indices). ``fields``: the launch's per-cell fields (``field_pair``). ``macro``: the
+        arrays of the density / velocity variant (``operands``), whose pointers every launch patches too."""
         key = (which, mask is not None) + tuple((tuple(t.shape), tuple(t.stride()), t.dtype, t.device)
                                                 for t in tensors) + \
-            ((tuple(force.shape), tuple(force.stride())) if force is not None else ()) + \
-            (('omf', tuple(omf.shape), tuple(omf.stride())) if omf is not None else ()) + \
-            (('sof', tuple(sof.shape), tuple(sof.stride())) if sof is not None else ()) + \
+            tuple((k, tuple(t.shape), tuple(t.stride())) for k, (t, _) in (fields or {}).items() if t is not None) + \
             ((fix[0].data_ptr(), int(fix[0].numel())) if fix is not None else ()) + \
             (('macro',) + tuple((n, tuple(t.stride())) for n, t in sorted(macro.items()) if t is not None)
              if macro else ())
@@ -408,15 +411,13 @@ class LatticeKernels:
         marr = self._macro_check(which, tuple(tensors[0].shape), macro) if macro else []
         if any(not t.is_cuda or t.device != tensors[0].device for t in marr):
             raise ValueError('the density / velocity arrays must be on the pdf tensors\' device')
-        self._field_check('force', tuple(tensors[0].shape), force, dforce, which)
-        self._field_check('omega', tuple(tensors[0].shape), omf, domf, which)
-        self._field_check('solid', tuple(tensors[0].shape), sof, dsof, which)
+        self._field_check(tuple(tensors[0].shape), fields, which)
         self._check(tensors, mask, ids)
-        if any(t is not None and (not t.is_cuda or t.device != tensors[0].device) for t in (omf, domf)):
-            raise ValueError('the relaxation-rate field must be on the pdf tensors\' device')
-        if any(t is not None and (not t.is_cuda or t.device != tensors[0].device) for t in (sof, dsof)):
-            raise ValueError('the solid-fraction field must be on the pdf tensors\' device')
-        idx, addr = self._launch_mode(tensors, force, dforce, omf, domf, *marr, sof=sof, dsof=dsof)
+        for f in CELL_FIELDS:
+            if any(t is not None and (not t.is_cuda or t.device != tensors[0].device)
+                   for t in field_pair(fields, f.kind)):
+                raise ValueError(f'the {f.what} must be on the pdf tensors\' device')
+        idx, addr = self._launch_mode(tensors, fields, marr)
         dev = tensors[0].device.index
         # (the fix-up kernel: the cell list and its length after the main kernel's arguments)
         kernel = which + ('_fix' if fix is not None else '')
@@ -425,8 +426,7 @@ class LatticeKernels:
         nblocks = self._blocks(X, Y, Z) if fix is None else -(-int(fix[0].numel()) // FIX_BLOCK)
         table = self.table(kernel, bool(macro))
         fmt = struct_format(table, idx, self.ct)
-        ops = dict(self.operands(tensors, mask, ids, force, dforce, omf, domf, macro=macro, sof=sof, dsof=dsof),
-                   cells=fix[0] if fix else None)
+        ops = dict(self.operands(tensors, mask, ids, fields, macro=macro), cells=fix[0] if fix else None)
         om_i = [a.kind for a in table].index(RATE)
         nptr = len((self._mptr_names if macro else self._ptr_names)[which])
         plan = self._plans[key] = LaunchPlan(fn, nblocks, _pack(fmt, *self._values(table, ops, omega)),
@@ -435,19 +435,16 @@ class LatticeKernels:
             plan.block = FIX_BLOCK
         return plan
 
-    def fix_launch(self, which, tensors, mask, omega, ids, force, dforce, cells, stream, omf=None, domf=None,
-                   macro=None, sof=None, dsof=None):
+    def fix_launch(self, which, tensors, mask, omega, ids, fields, cells, stream, macro=None):
         """The fix-up launch after a main adjoint launch on ``tensors`` (HIP with link programs; nothing for the
         forward, which runs them inline, or when no cell is listed): the listed cells' adjoint with their programs'
         Jacobian terms, added atomically into the entries the main launch left zeroed (no second fix-up launch)."""
         if which != 'adj' or self.programs is None or self.target != 'gpu' or cells is None or \
                 int(cells.numel()) == 0:
             return
-        plan = self.plan(which, tensors, mask, omega, ids, force, dforce, fix=(cells,), omf=omf, domf=domf,
-                         macro=macro, sof=sof, dsof=dsof)
+        plan = self.plan(which, tensors, mask, omega, ids, fields, fix=(cells,), macro=macro)
         rho = self.rho_buffer(tensors[0]) if self.link_pass else None
-        plan(self.pointers(which, self.operands(tensors, mask, ids, force, dforce, omf, domf, rho, macro, sof, dsof),
-                           bool(macro)), stream, omega)
+        plan(self.pointers(which, self.operands(tensors, mask, ids, fields, rho, macro), bool(macro)), stream, omega)
 
     def _scratch_shape(self, domain):
         """Of the second adjoint pass's scratch array: one value per cell (density-weighted links); with inline link
@@ -492,12 +489,8 @@ class LatticeKernels:
         and ``[*domain, D]``, any strides): also written, the density and the velocity of ``dst`` — 0 in obstacle
         cells — by the kernels' density / velocity variant."""
         macro = None if rho_out is None and vel_out is None else dict(rho_out=rho_out, vel_out=vel_out)
-        if self.target != 'gpu':
-            return self._cpu('fwd', [src, dst], omega, mask, ids, force, omf=omf, macro=macro, sof=sof)
-        st = _stream(stream, src)
-        self.plan('fwd', [src, dst], mask, omega, ids, force, omf=omf, macro=macro, sof=sof)(
-            self.pointers('fwd', self.operands([src, dst], mask, ids, force, omf=omf, macro=macro, sof=sof),
-                          bool(macro)), st, omega)
+        self.run('fwd', [src, dst], omega, mask, ids, dict(force=(force, None), omega=(omf, None), solid=(sof, None)),
+                 macro, cells, stream)
 
     def adjoint(self, src, g, out, omega, mask=None, stream=None, ids=None, force=None, dforce=None, cells=None,
                 omf=None, domf=None, rho_out=None, vel_out=None, drho=None, dvel=None, sof=None, dsof=None):
@@ -507,17 +500,22 @@ class LatticeKernels:
         adjoint seeds of the density and the velocity of this step's output, added to ``g`` in the cell (with the
         recorded ``rho_out`` / ``vel_out`` of that step, which a compressible rule reads)."""
         macro = None if drho is None and dvel is None else dict(rho_out=rho_out, vel_out=vel_out, drho=drho, dvel=dvel)
+        self.run('adj', [src, g, out], omega, mask, ids,
+                 dict(force=(force, dforce), omega=(omf, domf), solid=(sof, dsof)), macro, cells, stream)
+
+    def run(self, which, tensors, omega, mask=None, ids=None, fields=None, macro=None, cells=None, stream=None):
+        """One launch of ``which`` — 'fwd' on (src, dst), 'adj' on (src, g, out) with its fix-up launch and second pass
+        — what ``forward`` / ``adjoint`` do, which only turn their keywords into the bundle ``fields`` (``field_pair``)
+        and the by-name arrays ``macro`` (``operands``)."""
         if self.target != 'gpu':
-            return self._cpu('adj', [src, g, out], omega, mask, ids, force, dforce, omf, domf, macro, sof, dsof)
-        st = _stream(stream, src)
-        rho = self.rho_buffer(src) if self.link_pass else None
-        self.plan('adj', [src, g, out], mask, omega, ids, force, dforce, omf=omf, domf=domf, macro=macro, sof=sof,
-                  dsof=dsof)(
-            self.pointers('adj', self.operands([src, g, out], mask, ids, force, dforce, omf, domf, rho, macro, sof,
-                                               dsof), bool(macro)), st, omega)
-        self.fix_launch('adj', [src, g, out], mask, omega, ids, force, dforce, cells, st, omf, domf, macro, sof, dsof)
+            return self._cpu(which, tensors, omega, mask, ids, fields, macro)
+        st = _stream(stream, tensors[0])
+        rho = self.rho_buffer(tensors[0]) if which == 'adj' and self.link_pass else None
+        self.plan(which, tensors, mask, omega, ids, fields, macro=macro)(
+            self.pointers(which, self.operands(tensors, mask, ids, fields, rho, macro), bool(macro)), st, omega)
+        self.fix_launch(which, tensors, mask, omega, ids, fields, cells, st, macro)
         if rho is not None:
-            self.rho_pass(out, mask, rho, st)
+            self.rho_pass(tensors[2], mask, rho, st)
 
     def rho_pass(self, out, mask, rho, stream):
         """Launch the adjoint's second pass (``rho_plan``) for this launch's ``out``."""
@@ -543,8 +541,7 @@ class LatticeKernels:
             fn = self._fns[key] = compile_c(self.source(macro=macro), f'lbm_{which}', openmp=True)
         return fn
 
-    def _cpu(self, which, arrays, omega, mask, ids=None, force=None, dforce=None, omf=None, domf=None, macro=None,
-             sof=None, dsof=None):
+    def _cpu(self, which, arrays, omega, mask, ids=None, fields=None, macro=None):
         arrays = [np.asarray(a) for a in arrays]
         for a in arrays:
             if a.dtype != self.dtype:
@@ -553,16 +550,14 @@ class LatticeKernels:
         m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint32)
         idv = None if ids is None else np.ascontiguousarray(ids, dtype=np.uint8)
         shape = self._check_domain(arrays, m, idv)
-        self._field_check('force', shape, force, dforce, which, xp_tensor=False)
-        self._field_check('omega', shape, omf, domf, which, xp_tensor=False)
-        self._field_check('solid', shape, sof, dsof, which, xp_tensor=False)
+        self._field_check(shape, fields, which, xp_tensor=False)
         if macro:
             self._macro_check(which, shape, macro, xp_tensor=False)
         fn = self._cpu_fn(which, bool(macro))
         # the second pass's scratch (both passes in one call)
         rho = np.empty(self._scratch_shape(shape[:D]), self.dtype) if which == 'adj' and self.link_pass else None
         # ``P`` / ``S``: the table's pointers and strides, each in the table's order
-        ops = self.operands(arrays, m, idv, force, dforce, omf, domf, rho, macro, sof, dsof)
+        ops = self.operands(arrays, m, idv, fields, rho, macro)
         ptrs = self.pointers(which, ops, bool(macro))
         named = _stride_values(ops, D)
         strides = [named[a.name] for a in self.table(which, bool(macro)) if a.kind == STRIDE]

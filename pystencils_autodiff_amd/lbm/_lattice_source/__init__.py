@@ -5,7 +5,8 @@ target (HIP / C), the index type, the addressing mode and the adjoint mode — a
 (``lbm_fwd_cell``, ``collision``), the adjoint cell (``lbm_adj_cell``, ``adjoint``: prologue, moment-like sums, force
 adjoint, ω-field adjoint, scatter), the adjoint's second pass (``lbm_adj_rho_cell``, ``links``) and the entry points
 that call them for every cell (``entries``): HIP grid kernels, the HIP fix-up kernel over a cell list, or C loop
-nests. Every kernel's argument list is one table (``args.kernel_args``), which the launcher reads too. The
+nests. Every kernel's argument list is one table (``args.kernel_args``), which the launcher reads too, and the
+per-cell fields among the arguments are the rows of another (``fields.CELL_FIELDS``). The
 ``macroscopic`` variant (``macroscopic``) adds the density / velocity outputs to the forward cell and their adjoint
 seeds to the adjoint cell's load of ``g``; without the flag no line of any source changes.
 The ``solid_field`` variant (``solid``) blends the forward cell's stored value with the arriving population of the opposite
@@ -29,6 +30,7 @@ from .args import kernel_args, struct_format  # noqa: F401 (the launcher's)
 from .collision import forward_cell
 from .common import Context
 from .entries import c_entries, hip_fix_entry, hip_grid_entries
+from .fields import CELL_FIELDS  # noqa: F401 (the launcher's and the step's)
 from .links import link_tables, rho_cell
 from .smagorinsky import smagorinsky_rate
 from .spec import (ARRAYS, FIX_BIT, FIX_BLOCK, SELF_BIT, LatticeSource, density_links_message,  # noqa: F401

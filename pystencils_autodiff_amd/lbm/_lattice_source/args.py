@@ -2,6 +2,7 @@
 unpacking and the launcher's argument buffers (``_lattice_kernels``) are all read off ``kernel_args``."""
 from typing import NamedTuple
 
+from .fields import CELL_FIELDS
 from .spec import ARRAYS
 
 POINTER, EXTENT, STRIDE, REACH, RATE, CELLS, COUNT = 'pointer', 'extent', 'stride', 'reach', 'rate', 'cells', 'count'
@@ -66,19 +67,14 @@ def kernel_args(spec, kernel):
     adj = kernel == 'adj'
     pdfs = {'fwd': 'sd', 'adj': 'sgo'}[kernel]            # the pdf arrays of the cell function (the last one written)
     A = [_ptr(ARRAYS[p], 'pdf', const=p != pdfs[-1]) for p in pdfs] + [_MASK, _IDS]
-    if spec.ff:
-        A += [_ptr('force', 'force')] + ([_ptr('dforce', 'force', const=False)] if adj else [])
-    if spec.of:
-        A += [_ptr('omf', 'omega')] + ([_ptr('domega', 'omega', const=False)] if adj else [])
-    if spec.sf:
-        A += [_ptr('sigf', 'solid')] + ([_ptr('dsolid', 'solid', const=False)] if adj else [])
+    fields = [f for f in CELL_FIELDS if getattr(spec, f.flag)]
+    for f in fields:
+        A += [_ptr(f.operand, f.kind)] + ([_ptr(f.adjoint, f.kind, const=False)] if adj else [])
     if adj and spec.two:
         A += [_ptr('rho_adj', 'scratch', const=False)]
     A += macroscopic_pointers(spec, adj)
     A += _EXTENTS + [a for p in pdfs for a in _strides(p, 'qzyx', 'pdf')]
-    A += _strides('f', 'czyx', 'force') if spec.ff else []
-    A += _strides('w', 'zyx', 'omega') if spec.of else []
-    A += _strides('p', 'zyx', 'solid') if spec.sf else []
+    A += [a for f in fields for a in _strides(f.prefix, f.axes, f.kind)]
     A += _strides('r', 'zyx', 'macro') + _strides('v', 'czyx', 'macro') if spec.mo else []
     A += [Arg(f'{p}_bytes', REACH, f'const long long {p}_bytes', 'pdf') for p in pdfs]
     # (with an ω field the scalar rate is not what the collision reads: the cell loads ``omega``)

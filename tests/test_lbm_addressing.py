@@ -94,11 +94,11 @@ def test_launch_mode_force_field_widens_idx_only(dtype, monkeypatch):
     pdfs = [_meta(4096, dtype)] * 3
     near, far = _meta(I31 - 2, dtype), _meta(I31 - 1, dtype)
     assert K._launch_mode(pdfs) == ('int', 'buf')
-    assert K._launch_mode(pdfs, near, near) == ('int', 'buf')
-    assert K._launch_mode(pdfs[:2], far) == ('long long', 'buf')
-    assert K._launch_mode(pdfs, far, far) == ('long long', 'buf')
-    assert K._launch_mode(pdfs, near, far) == ('long long', 'buf')
-    assert K._launch_mode([_meta(I31 // 4, dtype)] * 3, far, far) == ('long long', 'ptr')
+    assert K._launch_mode(pdfs, {'force': (near, near)}) == ('int', 'buf')
+    assert K._launch_mode(pdfs[:2], {'force': (far, None)}) == ('long long', 'buf')
+    assert K._launch_mode(pdfs, {'force': (far, far)}) == ('long long', 'buf')
+    assert K._launch_mode(pdfs, {'force': (near, far)}) == ('long long', 'buf')
+    assert K._launch_mode([_meta(I31 // 4, dtype)] * 3, {'force': (far, far)}) == ('long long', 'ptr')
 
 
 # =================================================================================================================
@@ -743,8 +743,8 @@ def test_far_force_field_widens_idx_gpu():
         src = torch.tensor(case.f0, dtype=torch.float32, device='cuda')
         g = torch.tensor(case.g, dtype=torch.float32, device='cuda')
         dst, out = torch.empty_like(src), torch.empty_like(src)
-        assert K._launch_mode([src, dst], force) == ('long long', 'buf')
-        assert K._launch_mode([src, g, out], force, dforce) == ('long long', 'buf')
+        assert K._launch_mode([src, dst], {'force': (force, None)}) == ('long long', 'buf')
+        assert K._launch_mode([src, g, out], {'force': (force, dforce)}) == ('long long', 'buf')
         step._fwd(src, dst, {'F': force})
         step._bwd(src, g, out, {'F': force}, {step._adjoint_name(step._force_field): dforce})
         torch.cuda.synchronize()

@@ -444,8 +444,8 @@ def test_omega_field_sources_compile(monkeypatch):
     pdfs = [torch.empty((6, 5, 9), dtype=torch.float32, device='meta')] * 3
     far = torch.empty_strided((6, 5), (2 ** 31 // 5, 1), dtype=torch.float32, device='meta')
     near = torch.empty((6, 5), dtype=torch.float32, device='meta')
-    assert K._launch_mode(pdfs, omf=near, domf=near) == ('int', 'buf')
-    assert K._launch_mode(pdfs, omf=far, domf=far) == ('long long', 'buf')
+    assert K._launch_mode(pdfs, {'omega': (near, near)}) == ('int', 'buf')
+    assert K._launch_mode(pdfs, {'omega': (far, far)}) == ('long long', 'buf')
 
 
 # --- GPU -------------------------------------------------------------------------------------------------------

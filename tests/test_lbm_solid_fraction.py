@@ -670,9 +670,9 @@ def test_solid_fraction_source_variants_differ_and_c_builds():
     pdfs = [torch.empty((6, 5, 9), dtype=torch.float32, device='meta')] * 3
     far = torch.empty_strided((6, 5), (2 ** 31 // 5, 1), dtype=torch.float32, device='meta')
     near = torch.empty((6, 5), dtype=torch.float32, device='meta')
-    assert K._launch_mode(pdfs, sof=near, dsof=near) == ('int', 'buf')
-    assert K._launch_mode(pdfs, sof=far, dsof=far) == ('long long', 'buf')
-    assert K._launch_mode(pdfs, sof=near, dsof=far) == ('long long', 'buf')
+    assert K._launch_mode(pdfs, {'solid': (near, near)}) == ('int', 'buf')
+    assert K._launch_mode(pdfs, {'solid': (far, far)}) == ('long long', 'buf')
+    assert K._launch_mode(pdfs, {'solid': (near, far)}) == ('long long', 'buf')
 
 
 # --- GPU -------------------------------------------------------------------------------------------------------
